@@ -25,6 +25,13 @@ per GPU; ``--batch 16384`` reproduces the smaller configuration).  The reference
 no number; ``vs_baseline`` is against the reference's derived
 data-delivery ceiling of 25,478 samples/s per worker (BASELINE.md row
 "Derived: data-delivery ceiling"), i.e. 25,478 * N.
+
+A plain run does only what the headline needs: shard delivery, warm-up, the timed
+steps, the JSON line.  ``--full`` adds the measurements that take runs of their own
+(the settled-clock replay, ``settled_*``).  ``--dump-outputs DIR`` writes the state
+the last timed step left (parameters, momentum, per-sample loss / correctness) as
+``DIR/<name>.npy``; shards and initial weights are seeded, so the same arguments
+give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -80,10 +87,19 @@ def parse(argv=None):
                          "chunks, its logging and feedback); 1 GPU")
     ap.add_argument("--graph-steps", type=int, default=0,
                     help="--runtime: steps per worker graph chunk (0: the runtime's default, config.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline value does not need: the settled-clock replay (--settle). "
+                         "A plain run sets up, warms up, times the K steps and prints the JSON line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them left behind as DIR/<name>.npy "
+                         "(float32 / float64): the trained parameters, the momentum, the last batch's per-sample "
+                         "loss and correctness, and [mean loss, accuracy].  Arrays of more than 4 Mi elements are "
+                         "written as a fixed, seeded sample.  Same arguments, same inputs: two builds compare "
+                         "output for output")
     ap.add_argument("--settle", type=float, default=0.3,
-                    help="after the timed region (1 GPU, graph mode): replay the same K-step graph back-to-back "
-                         "for this many seconds and report the last replay as settled_* fields (informative; the "
-                         "headline value is the timed region).  0 disables")
+                    help="--full, after the timed region (1 GPU, graph mode): replay the same K-step graph "
+                         "back-to-back for this many seconds and report the last replay as settled_* fields "
+                         "(informative; the headline value is the timed region).  0 disables")
     ap.add_argument("--graph-collectives", action="store_true",
                     default=os.environ.get("SL_GRAPH_COLLECTIVES", "0") == "1",
                     help="N>1 with RCCL: capture the process group's collectives (the MLP all-reduce hook, the "
@@ -248,6 +264,35 @@ def record(args, *, world, elapsed, model_name, n_params, use_graph, collective,
     return out
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: the four float32 arrays stay under 64 MB together
+
+
+def dump_outputs(tr, st, out_dir: str) -> dict:
+    """``--dump-outputs DIR``: what the timed steps left in the trainer ``tr``, one ``.npy`` per
+    array.  ``params`` / ``momentum`` are the fp32 master weights and their momentum after the last
+    timed step, ``loss`` / ``correct`` that step's per-sample values, ``stats`` (float64) their means
+    ``st``.  An array longer than ``DUMP_MAX_ELEMS`` is written as the elements at a fixed, seeded,
+    sorted set of indices, the same in every run.  Returns {name: elements written}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = tr.get_flat().numel()
+    arrays = {"params": tr.get_flat(), "momentum": None if tr.mom is None else tr.mom[:n],
+              "loss": tr.loss, "correct": tr.correct}
+    written = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = int(a.size)
+    np.save(os.path.join(out_dir, "stats.npy"), np.array([st.loss, st.accuracy], dtype=np.float64))
+    written["stats"] = 2
+    return written
+
+
 def runtime_bench(args, dev) -> tuple[float, dict, object]:
     """``--runtime``: the reference's three roles end-to-end on this GPU (file_server.cc,
     master.cc, worker.cc).  The file server streams the shard to the worker over gRPC, the
@@ -339,6 +384,8 @@ def main(argv=None) -> int:
         out["config"]["mode"] = "runtime"
         out["config"]["steps_per_graph"] = rt_info["graph_steps"]
         out["runtime"] = rt_info
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(tr, tr.stats(), args.dump_outputs)
         print(json.dumps(out), flush=True)
         if args.json_out:
             with open(args.json_out, "w") as f:
@@ -623,8 +670,11 @@ def main(argv=None) -> int:
             return 2
         if re_elapsed is not None:
             elapsed = re_elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything below steps the trainer again
+        dumped = dump_outputs(tr, st_timed, args.dump_outputs)
     settled = None
-    if world == 1 and use_graph and args.settle > 0:
+    if args.full and world == 1 and use_graph and args.settle > 0:
         # Informative only: the same K-step replay, back-to-back for args.settle seconds, then
         # one replay timed the same way.  The gap to the headline is the GPU clock still ramping
         # up from the idle ingest when the timed region starts (profiles/r03_final2).
@@ -640,6 +690,8 @@ def main(argv=None) -> int:
         out["settled_samples_per_s"] = round(args.batch * args.steps / settled, 1)
     if fallback:
         out["replica_fallback"] = fallback
+    if dumped:
+        out["dumped_outputs"] = dumped
     if getattr(tr, "probe", None) is not None:
         # per step: wall us between consecutive probes and the shader clock over it (GHz), per XCD
         # where both probes ran a workgroup on that XCD (median over those XCDs)

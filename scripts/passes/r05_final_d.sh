@@ -11,7 +11,7 @@ rc=$?; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('SMOKE_OK')" > $O/smoke.log 2>&1 || exit 1
 tail -1 $O/smoke.log
 for rep in 1 2 3 4 5; do
-  timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_mlp_$rep.log 2>&1 || exit 1
+  timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_mlp_$rep.log 2>&1 || exit 1
   echo "mlp $rep $(grep -o '"value": [0-9.]*\|"settled_samples_per_s": [0-9.]*' $O/bench_mlp_$rep.log | tr '\n' ' ')"
 done
 for rep in 1 2 3; do
@@ -23,7 +23,7 @@ python scripts/rocprof_summary.py $O/prof_mlp/run_results.db > $O/kernels_mlp.cs
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_resnet -o run -- python3 bench.py --model resnet18 --steps 20 --warmup 5 --settle 0 > $O/prof_resnet.log 2>&1 || exit 1
 python scripts/rocprof_summary.py $O/prof_resnet/run_results.db > $O/kernels_resnet18.csv; rm -rf $O/prof_resnet; head -4 $O/kernels_resnet18.csv | cut -c1-100
 for b in 16384 32768 65536 131072 262144; do
-  timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --batch $b --ingest local > $O/sweep_mlp_$b.log 2>&1 || exit 1
+  timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --batch $b --ingest local --full > $O/sweep_mlp_$b.log 2>&1 || exit 1
   echo "mlp B=$b $(grep -o '"value": [0-9.]*\|"settled_samples_per_s": [0-9.]*' $O/sweep_mlp_$b.log | tr '\n' ' ')"
 done
 for b in 256 512 2048; do

@@ -10,7 +10,7 @@ V=serverless_learn_amd/_native/variants
 for rep in 1 2 3 4; do
   for v in base nt ntw; do
     so=""; [ $v != base ] && so=$V/libslkernels_$v.so
-    SL_KERNELS_SO=$so timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/m_${v}_$rep.json 2> $O/m_${v}_$rep.err || exit 4
+    SL_KERNELS_SO=$so timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full > $O/m_${v}_$rep.json 2> $O/m_${v}_$rep.err || exit 4
     echo "$v rep=$rep $(grep -o '"value": [0-9.]*\|"settled_samples_per_s": [0-9.]*' $O/m_${v}_$rep.json | tr '\n' ' ')"
   done
 done

@@ -157,6 +157,40 @@ def test_bench_prints_the_driver_json_contract(argv, capsys):
             assert out["metric"] == json.load(f)["metric"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, capsys):
+    """A plain bench.py run reports no settled_* fields (the settled-clock replay belongs to
+    --full) and --dump-outputs writes the state the last timed step left: float32 arrays of the
+    trainer's sizes, stats.npy equal to the JSON's last loss / accuracy; with --full the settled
+    replay runs after the dump, so the dumped state is still the timed steps'."""
+    import json
+
+    import numpy as np
+
+    import bench
+    from serverless_learn_amd.models.mlp import N_PARAMS
+
+    argv = ["--steps", "4", "--warmup", "2", "--ingest", "local", "--batch", "4096"]
+    outs = []
+    for extra in ([], ["--full", "--settle", "0.05"]):
+        d = tmp_path / ("full" if extra else "plain")
+        assert bench.main(argv + extra + ["--dump-outputs", str(d)]) == 0
+        out = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+        assert ("settled_ms_per_step" in out) == bool(extra) and out["steps"] == 4
+        arrays = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(arrays) == {"params", "momentum", "loss", "correct", "stats"} == set(out["dumped_outputs"])
+        assert arrays["params"].shape == arrays["momentum"].shape == (N_PARAMS,)
+        assert arrays["loss"].shape == arrays["correct"].shape == (4096,)
+        assert all(a.dtype == (np.float64 if k == "stats" else np.float32) for k, a in arrays.items())
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        assert abs(arrays["stats"][0] - out["train_loss_last"]) < 1e-4
+        assert abs(arrays["stats"][1] - out["train_acc_last"]) < 1e-4
+        assert abs(arrays["loss"].mean() - arrays["stats"][0]) < 1e-4
+        outs.append(arrays)
+    # same arguments, same seeded inputs: both runs trained the same model (split-K atomics
+    # reorder fp32 sums, so equal to rounding, not bitwise)
+    assert np.allclose(outs[0]["params"], outs[1]["params"], rtol=0, atol=1e-3)
+
+
 def test_bench_two_ranks_autotune_and_replicas():
     """bench.py with 2 ranks (gloo rehearsal on the one GPU): the xGMI exchange is set up, one-shot,
     two-shot and the process group are timed before the timed region, the replicas end identical,

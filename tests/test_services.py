@@ -187,7 +187,11 @@ def test_idempotent_rpc_retries_until_listener_is_back(ch):
     started = {}
 
     def start_later():
-        time.sleep(0.4)
+        # the listener comes up once the first attempt has failed and been re-sent -- not after
+        # a fixed sleep, which raced the client's whole back-off budget (0.4-1.1 s by its jitter)
+        t_end = time.monotonic() + 4.0
+        while ch.retried < 1 and time.monotonic() < t_end:
+            time.sleep(0.002)
         started["fs"] = FileServer(fast_config(shard_records=256), addr=addr).start()
 
     th = threading.Thread(target=start_later)

@@ -341,6 +341,37 @@ def test_bench_replica_check_covers_every_path_and_refuses_persistent_divergence
     assert bench.parse(["--graph-collectives"]).graph_collectives is True
 
 
+def test_bench_dump_outputs_writes_seeded_samples_of_large_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: every array is written as float32 (stats as float64); one longer than the
+    cap is written as the same seeded, sorted sample in every run; --full and --dump-outputs are
+    off by default."""
+    import bench
+    from serverless_learn_amd.models.mlp import StepStats
+
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and bench.parse(["--full"]).full is True
+
+    class Tr:
+        mom = torch.arange(12, dtype=torch.float32)  # padded past the 10 parameters
+        loss = torch.ones(4, dtype=torch.float64)
+        correct = torch.zeros(4)
+
+        def get_flat(self):
+            return torch.arange(10, dtype=torch.float32) * 2
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 6)
+    runs = []
+    for d in ("a", "b"):
+        n = bench.dump_outputs(Tr(), StepStats(1.0, 0.0, 4), str(tmp_path / d))
+        assert n == {"params": 6, "momentum": 6, "loss": 4, "correct": 4, "stats": 2}
+        runs.append({k: np.load(tmp_path / d / f"{k}.npy") for k in n})
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k])
+        assert runs[0][k].dtype == (np.float64 if k == "stats" else np.float32)
+    assert np.array_equal(runs[0]["params"], 2 * runs[0]["momentum"])  # the same indices, below 10
+    assert np.all(np.diff(runs[0]["params"]) > 0) and list(runs[0]["stats"]) == [1.0, 0.0]
+
+
 def test_ps_new_incarnation_restarts_old_and_anonymous_entries_are_bounded():
     from serverless_learn_amd.parallel.ps import ParameterServer
 
