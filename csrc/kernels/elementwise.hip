@@ -85,6 +85,88 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ w, co
   }
 }
 
+// K5 under a rule that depends on the optimizer step (a device-resident counter, so a captured
+// graph replays it with a moving learning rate): AdamW (torch.optim.AdamW: decoupled weight
+// decay, bias correction, no amsgrad; mom is the first moment, v the second) or momentum SGD
+// with a scheduled learning rate.  Same walk as sgd_flat_kernel.  This launch only reads the
+// step; the engine bumps it with its cursor launcher afterwards.
+struct FlatOpt {
+  const int* step;      // updates applied so far
+  const float* lr_tab;  // lr_tab[min(step, lr_last)] is this step's lr; nullptr: lr
+  int lr_last;
+  float lr, mu, wd, gscale;
+  // from the host, each computed in double and rounded once (1 - 0.999f is 3e-5 off; 1 - b^t
+  // cancels at small t: ln b and expm1)
+  float b1, b2, omb1, omb2, lnb1, lnb2, eps;
+};
+
+template <bool ADAMW>
+__global__ __launch_bounds__(256) void opt_flat_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                       float* __restrict__ mom, float* __restrict__ v,
+                                                       uint16_t* __restrict__ shadow, long n, FlatOpt o) {
+  // wave-uniform scalars of the step, ahead of the loads
+  const int k = *o.step;
+  const float lr = o.lr_tab ? o.lr_tab[k < o.lr_last ? k : o.lr_last] : o.lr;
+  float keep = 1.f, ssz = 0.f, rbc2 = 0.f;
+  if constexpr (ADAMW) {
+    const float t = (float)k + 1.f;
+    keep = 1.f - lr * o.wd;
+    ssz = lr / -expm1f(t * o.lnb1);
+    rbc2 = 1.f / sqrtf(-expm1f(t * o.lnb2));
+  }
+  auto apply = [&](float& wj, float gj, float& mj, float& vj) __attribute__((always_inline)) {
+    const float gs = gj * o.gscale;
+    if constexpr (ADAMW) {
+      mj = fmaf(o.b1, mj, o.omb1 * gs);
+      vj = fmaf(o.b2, vj, o.omb2 * gs * gs);
+      wj = fmaf(-ssz, mj / fmaf(sqrtf(vj), rbc2, o.eps), wj * keep);
+    } else {
+      float d = gs + o.wd * wj;
+      if (mom) { d = o.mu * mj + d; mj = d; }
+      wj -= lr * d;
+    }
+  };
+  const long stride = (long)gridDim.x * blockDim.x * 4;
+  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      float4 wv = *reinterpret_cast<float4*>(w + i);
+      const float4 gv = *reinterpret_cast<const float4*>(g + i);
+      float wa[4] = {wv.x, wv.y, wv.z, wv.w};
+      const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
+      float ma[4] = {0.f, 0.f, 0.f, 0.f}, va[4] = {0.f, 0.f, 0.f, 0.f};
+      if (mom) {
+        const float4 mv = *reinterpret_cast<const float4*>(mom + i);
+        ma[0] = mv.x; ma[1] = mv.y; ma[2] = mv.z; ma[3] = mv.w;
+      }
+      if constexpr (ADAMW) {
+        const float4 vv = *reinterpret_cast<const float4*>(v + i);
+        va[0] = vv.x; va[1] = vv.y; va[2] = vv.z; va[3] = vv.w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) apply(wa[j], ga[j], ma[j], va[j]);
+      *reinterpret_cast<float4*>(w + i) = make_float4(wa[0], wa[1], wa[2], wa[3]);
+      if (mom) *reinterpret_cast<float4*>(mom + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+      if constexpr (ADAMW) *reinterpret_cast<float4*>(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+      if (shadow) {
+        uint2 pk;
+        pk.x = pack2(wa[0], wa[1]);
+        pk.y = pack2(wa[2], wa[3]);
+        *reinterpret_cast<uint2*>(shadow + i) = pk;
+      }
+    } else {
+      for (long q = i; q < n; ++q) {
+        float wq = w[q], mq = mom ? mom[q] : 0.f, vq = 0.f;
+        if constexpr (ADAMW) vq = v[q];
+        apply(wq, g[q], mq, vq);
+        w[q] = wq;
+        if (mom) mom[q] = mq;
+        if constexpr (ADAMW) v[q] = vq;
+        if (shadow) shadow[q] = f2bf(wq);
+      }
+    }
+  }
+}
+
 // f32 -> bf16 copy (shadow refresh after load / broadcast).
 __global__ __launch_bounds__(256) void to_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, long n) {
   const long stride = (long)gridDim.x * blockDim.x;
@@ -123,6 +205,39 @@ int sl_sgd_flat(float* w, const float* g, float* mom, uint16_t* shadow, long n, 
   if (((uintptr_t)w | (uintptr_t)g | (uintptr_t)(mom ? mom : w)) & 15) return -1;
   if (shadow && ((uintptr_t)shadow & 7)) return -1;
   hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom, shadow, n, lr, mu, wd, gscale);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool flat_opt_ok(const float* w, const float* g, const float* mom, const float* v, const uint16_t* shadow,
+                        const int* step, const float* lr_tab, int lr_n) {
+  if (!w || !g || !step || (lr_tab && lr_n < 1)) return false;
+  if (((uintptr_t)w | (uintptr_t)g | (uintptr_t)(mom ? mom : w) | (uintptr_t)(v ? v : w)) & 15) return false;
+  return !(shadow && ((uintptr_t)shadow & 7));
+}
+
+// AdamW over the flat vector; the learning rate of step *step is lr_tab[min(*step, lr_n - 1)]
+// (nullptr: lr).  The caller advances *step after this launch.
+int sl_adamw_flat(float* w, const float* g, float* mom, float* v, uint16_t* shadow, long n, const int* step,
+                  const float* lr_tab, int lr_n, float lr, float wd, float gscale, float b1, float b2, float omb1,
+                  float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!mom || !v || !flat_opt_ok(w, g, mom, v, shadow, step, lr_tab, lr_n)) return -1;
+  if (!(lnb1 < 0.f) || !(lnb2 < 0.f) || !(eps > 0.f)) return -1;  // bias corrections divide by 1 - b^t
+  const FlatOpt o = {step, lr_tab, lr_tab ? lr_n - 1 : 0, lr, 0.f, wd, gscale, b1, b2, omb1, omb2, lnb1, lnb2, eps};
+  hipLaunchKernelGGL(opt_flat_kernel<true>, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom, v, shadow, n, o);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// sl_sgd_flat with the learning rate of step *step from a table (see sl_adamw_flat)
+int sl_sgd_flat_lr(float* w, const float* g, float* mom, uint16_t* shadow, long n, const int* step,
+                   const float* lr_tab, int lr_n, float mu, float wd, float gscale, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!lr_tab || !flat_opt_ok(w, g, mom, nullptr, shadow, step, lr_tab, lr_n)) return -1;
+  const FlatOpt o = {step, lr_tab, lr_n - 1, 0.f, mu, wd, gscale, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  hipLaunchKernelGGL(opt_flat_kernel<false>, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom,
+                     static_cast<float*>(nullptr), shadow, n, o);
   SL_CHECK_LAUNCH();
   return 0;
 }

@@ -31,6 +31,8 @@
 //           bf16 shadow weights (and the transposed copies the backward pass
 //           reads) in the same pass; bumps the device batch cursor so the
 //           whole step replays from a hipGraph without host work.
+//           (mlp_opt_kernel / mlp_opt_update_kernel: the same launches under AdamW or a
+//           scheduled lr, reading the device-resident optimizer step -- sgd_apply<RULE>)
 #include "common.h"
 #include "xgmi.h"
 
@@ -1626,18 +1628,90 @@ __device__ __forceinline__ float quad_sum(float v) {
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
 }
 
-// w0 / m0: the parameter and momentum, loaded by the caller ahead of the slab sums.  Returns
-// write_shadow's fixed-point fp16 W1 value.
-__device__ __forceinline__ long long sgd_apply(const SgdArgs& a, float* gout, long p, float gme, float w0, float m0) {
+// The update rule is a compile-time parameter of the update kernels.  RULE_SGD is momentum
+// SGD with the launch's scalar lr (no step counter); the other two read the device-resident
+// optimizer step, so a captured graph replays them with a moving learning rate:
+//   RULE_SGD_LR  momentum SGD, lr from the schedule table
+//   RULE_ADAMW   torch.optim.AdamW (decoupled weight decay, bias correction, no amsgrad);
+//                a.mom is the first moment, o.v the second; lr from the table or a.lr
+constexpr int RULE_SGD = 0, RULE_SGD_LR = 1, RULE_ADAMW = 2;
+
+struct OptArgs {
+  float* v;             // AdamW second moment
+  int* step;            // optimizer step: updates applied so far (0-based step of this launch)
+  unsigned* ticket;     // workgroups of this launch that are done with `step` (opt_end)
+  const float* lr_tab;  // lr_tab[min(step, lr_last)] is this step's lr; nullptr: a.lr
+  int lr_last;
+  // from the host, each computed in double and rounded once: 1 - 0.999f is 3e-5 off, and
+  // 1 - b^t cancels at small t (hence ln b and expm1)
+  float b1, b2, omb1, omb2, lnb1, lnb2, eps;
+};
+
+// What a launch derives from the step: wave-uniform, computed once per thread at kernel start
+struct OptStep {
+  int k;       // the step read
+  float lr;    // this step's learning rate
+  float keep;  // AdamW: 1 - lr wd
+  float ssz;   // AdamW: lr / (1 - b1^t)
+  float rbc2;  // AdamW: 1 / sqrt(1 - b2^t)
+};
+
+template <int RULE>
+__device__ __forceinline__ OptStep opt_begin(const SgdArgs& a, const OptArgs& o) {
+  OptStep s = {};
+  if constexpr (RULE != RULE_SGD) {
+    s.k = __hip_atomic_load(o.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s.lr = o.lr_tab ? o.lr_tab[s.k < o.lr_last ? s.k : o.lr_last] : a.lr;
+    if constexpr (RULE == RULE_ADAMW) {
+      const float t = (float)s.k + 1.f;
+      s.keep = 1.f - s.lr * a.wd;
+      s.ssz = s.lr / -expm1f(t * o.lnb1);
+      s.rbc2 = 1.f / sqrtf(-expm1f(t * o.lnb2));
+    }
+  }
+  return s;
+}
+
+// Every workgroup read the step at its start (opt_begin); the one that draws the last ticket
+// knows all of them have, and advances it.  (Bumping at kernel start, as the batch cursor is,
+// would race with the other workgroups' reads: nothing in this launch consumes the cursor.)
+// The count is relaxed, as xg_finish's is (xgmi.h): a workgroup's read has completed before
+// its barrier here, so the advance cannot overtake it; the update's other writes reach later
+// kernels through the kernel boundary.
+__device__ __forceinline__ void opt_end(const OptArgs& o, const OptStep& s) {
+  __syncthreads();  // every wave of this workgroup is past its read
+  if (threadIdx.x == 0) {
+    const unsigned n = __hip_atomic_fetch_add(o.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (n + 1u == gridDim.x) {
+      __hip_atomic_store(o.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(o.step, s.k + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// w0 / m0 / v0: the parameter and its optimizer state, loaded by the caller ahead of the slab
+// sums.  The single place the rule lives.  Returns write_shadow's fixed-point fp16 W1 value.
+template <int RULE>
+__device__ __forceinline__ long long sgd_apply(const SgdArgs& a, const OptArgs& o, const OptStep& s, float* gout,
+                                               long p, float gme, float w0, float m0, float v0) {
   if (gout) gout[p] = gme;
   if (a.mode == 1) return 0;
   float w = w0;
-  float d = gme + a.wd * w;
-  if (a.mom) {
-    d = a.mu * m0 + d;
-    a.mom[p] = d;
+  if constexpr (RULE == RULE_ADAMW) {
+    // explicit fma: the same bits from every kernel that carries the rule
+    const float m = fmaf(o.b1, m0, o.omb1 * gme);
+    const float v = fmaf(o.b2, v0, o.omb2 * gme * gme);
+    a.mom[p] = m;
+    o.v[p] = v;
+    w = fmaf(-s.ssz, m / fmaf(sqrtf(v), s.rbc2, o.eps), w0 * s.keep);
+  } else {
+    float d = gme + a.wd * w;
+    if (a.mom) {
+      d = a.mu * m0 + d;
+      a.mom[p] = d;
+    }
+    w -= (RULE == RULE_SGD ? a.lr : s.lr) * d;
   }
-  w -= a.lr * d;
   a.w[p] = w;
   return write_shadow(a, p, w);
 }
@@ -1659,7 +1733,9 @@ __device__ __forceinline__ float group_sum(float v) {
 // single parameters).  w / mom / the shadows are then touched in a scattered order, but they
 // are 1 MB arrays that stay in L2.
 // Returns this thread's fixed-point fp16 W1 weight (mode 2), for the row sums.
-__device__ __forceinline__ long long sgd_tiled(const SgdArgs& a, long u, int part) {
+template <int RULE>
+__device__ __forceinline__ long long sgd_tiled(const SgdArgs& a, const OptArgs& o, const OptStep& os, long u,
+                                               int part) {
   const long off = u * 4;
   if (off >= TL_SMALL + W3P_LD) return 0;
   long pe = -1;       // this thread's parameter (part < 4)
@@ -1688,6 +1764,8 @@ __device__ __forceinline__ long long sgd_tiled(const SgdArgs& a, long u, int par
   const bool upd = mine && a.mode != 1;
   const float w0 = upd ? a.w[pe] : 0.f;
   const float m0 = upd && a.mom ? a.mom[pe] : 0.f;
+  float v0 = 0.f;
+  if constexpr (RULE == RULE_ADAMW) v0 = upd ? o.v[pe] : 0.f;
   float g[4] = {0.f, 0.f, 0.f, 0.f};
   float db = 0.f;
   const float* src = a.slab + off;
@@ -1720,7 +1798,7 @@ __device__ __forceinline__ long long sgd_tiled(const SgdArgs& a, long u, int par
   if (!mine) return 0;
   float* gout = a.grad_out;
   if (a.ar_ctl && (xg_cur(a.ar_ctl, a.xg.inline_sync) & 1u)) gout = a.grad_out_alt;
-  return sgd_apply(a, gout, pe, gme, w0, m0);
+  return sgd_apply<RULE>(a, o, os, gout, pe, gme, w0, m0, v0);
 }
 
 // float4 units a launch of mlp_sgd_kernel walks: the slab's (tiled) or the parameters'
@@ -1728,13 +1806,14 @@ __host__ __device__ constexpr long sgd_units(bool slab) {
   return slab ? TL_STRIDE / 4 : (P_N + 3) / 4;
 }
 
-__global__ __launch_bounds__(SGD_NT) void mlp_sgd_kernel(SgdArgs a) {
+template <int RULE>
+__device__ __forceinline__ void mlp_sgd_body(const SgdArgs& a, const OptArgs& o, const OptStep& os) {
   if (a.cursor && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.cursor, 1);
   if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 2] = __builtin_amdgcn_s_memrealtime();
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int part = (int)(t % SGD_TPG);
   if (a.slab && a.mode != 0) {
-    const long long fx = sgd_tiled(a, t / SGD_TPG, part);
+    const long long fx = sgd_tiled<RULE>(a, o, os, t / SGD_TPG, part);
     // W1 row sums: a workgroup of the tiled walk covers 128 units of one tile = 16 rows
     // (m_base + lane & 15) x 32 columns (one R1 block) of W1; its 512 fixed-point values are
     // summed per row in LDS (integer: order-free, exact) and written as that block's partials
@@ -1776,7 +1855,21 @@ __global__ __launch_bounds__(SGD_NT) void mlp_sgd_kernel(SgdArgs a) {
   if (!mine) return;
   float* gout = a.grad_out;
   if (a.ar_ctl && (xg_cur(a.ar_ctl, a.xg.inline_sync) & 1u)) gout = a.grad_out_alt;
-  sgd_apply(a, gout, p, gme, w0, m0);
+  float v0 = 0.f;
+  if constexpr (RULE == RULE_ADAMW) v0 = upd ? o.v[p] : 0.f;
+  sgd_apply<RULE>(a, o, os, gout, p, gme, w0, m0, v0);
+}
+
+__global__ __launch_bounds__(SGD_NT) void mlp_sgd_kernel(SgdArgs a) {
+  mlp_sgd_body<RULE_SGD>(a, OptArgs{}, OptStep{});
+}
+
+// The tiled slab reduction + update (mode 2) under a rule that reads the optimizer step
+template <int RULE>
+__global__ __launch_bounds__(SGD_NT) void mlp_opt_kernel(SgdArgs a, OptArgs o) {
+  const OptStep os = opt_begin<RULE>(a, o);
+  mlp_sgd_body<RULE>(a, o, os);
+  opt_end(o, os);
 }
 
 // Fixed-point partial row sums of the fp16 W1 shadow, for the update paths that do not walk the
@@ -1819,8 +1912,9 @@ __device__ __forceinline__ float4 xg_load_reduced_any(const XgArgs& x, unsigned 
   return owner == lo ? va : vb;
 }
 
-template <bool XG>
-__global__ __launch_bounds__(UPD_NT) void mlp_update_kernel(SgdArgs a, XgArgs x) {
+template <bool XG, int RULE>
+__device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& x, const OptArgs& o,
+                                                const OptStep& os) {
   __shared__ unsigned s_step;
   const int tid = threadIdx.x;
   if (a.cursor && blockIdx.x == 0 && tid == 0) atomicAdd(a.cursor, 1);
@@ -1835,11 +1929,12 @@ __global__ __launch_bounds__(UPD_NT) void mlp_update_kernel(SgdArgs a, XgArgs x)
   };
   long i4 = 0, ic = 0;
   bool live = false;
-  float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = w4;
+  float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = w4, v4 = w4;
   if (SL_UPD_HOIST && (int)blockIdx.x < UPD_TASKS) {
     item(blockIdx.x, i4, ic, live);
     w4 = reinterpret_cast<const float4*>(a.w)[ic];
     if (a.mom) m4 = reinterpret_cast<const float4*>(a.mom)[ic];
+    if constexpr (RULE == RULE_ADAMW) v4 = reinterpret_cast<const float4*>(o.v)[ic];
   }
   unsigned s = 0;
   float4 own = make_float4(0.f, 0.f, 0.f, 0.f);  // one-shot: this rank's own slot, first work item
@@ -1856,6 +1951,7 @@ __global__ __launch_bounds__(UPD_NT) void mlp_update_kernel(SgdArgs a, XgArgs x)
       item(task, i4, ic, live);
       w4 = reinterpret_cast<const float4*>(a.w)[ic];
       m4 = a.mom ? reinterpret_cast<const float4*>(a.mom)[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (RULE == RULE_ADAMW) v4 = reinterpret_cast<const float4*>(o.v)[ic];
     }
     float4 g;
     if constexpr (XG) {
@@ -1881,9 +1977,10 @@ __global__ __launch_bounds__(UPD_NT) void mlp_update_kernel(SgdArgs a, XgArgs x)
     long long fx = 0;
     if (live) {
       const float ga[4] = {g.x, g.y, g.z, g.w}, wa[4] = {w4.x, w4.y, w4.z, w4.w}, ma[4] = {m4.x, m4.y, m4.z, m4.w};
+      const float va[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (i4 * 4 + j < P_N) fx += sgd_apply(a, nullptr, i4 * 4 + j, ga[j], wa[j], ma[j]);
+        if (i4 * 4 + j < P_N) fx += sgd_apply<RULE>(a, o, os, nullptr, i4 * 4 + j, ga[j], wa[j], ma[j], va[j]);
     }
     if (w1) {  // 32-column block b = lanes 8b .. 8b+7 of the row (the 25th: 4 live lanes + 4 dead)
       fx += __shfl_xor(fx, 1);
@@ -1895,6 +1992,19 @@ __global__ __launch_bounds__(UPD_NT) void mlp_update_kernel(SgdArgs a, XgArgs x)
   if constexpr (XG) {
     if (!x.inline_sync) xg_finish(x, s);  // inline: the next step's rows kernel advances the step
   }
+}
+
+template <bool XG>
+__global__ __launch_bounds__(UPD_NT) void mlp_update_kernel(SgdArgs a, XgArgs x) {
+  mlp_update_body<XG, RULE_SGD>(a, x, OptArgs{}, OptStep{});
+}
+
+// The same update under a rule that reads the optimizer step (the wait / abort code is the body's)
+template <bool XG, int RULE>
+__global__ __launch_bounds__(UPD_NT) void mlp_opt_update_kernel(SgdArgs a, XgArgs x, OptArgs o) {
+  const OptStep os = opt_begin<RULE>(a, o);
+  mlp_update_body<XG, RULE>(a, x, o, os);
+  opt_end(o, os);
 }
 
 // ---------------------------------------------------------------------------
@@ -2049,6 +2159,59 @@ int sl_mlp_sgd(float* w, float* mom, const float* slab, int slices, long slab_st
   return 0;
 }
 
+// The rules that read the optimizer step (RULE_SGD_LR / RULE_ADAMW): their arguments, checked.
+static bool opt_fill(OptArgs& o, int rule, const float* mom, float* v, int* step, unsigned* ticket,
+                     const float* lr_tab, int lr_n, float b1, float b2, float omb1, float omb2, float lnb1,
+                     float lnb2, float eps) {
+  if (rule != RULE_SGD_LR && rule != RULE_ADAMW) return false;
+  if (!step || !ticket) return false;
+  if (lr_tab ? lr_n < 1 : rule == RULE_SGD_LR) return false;  // scheduled SGD has no scalar-lr form here
+  if (rule == RULE_ADAMW) {
+    if (!mom || !v || ((uintptr_t)v & 15)) return false;
+    if (!(lnb1 < 0.f) || !(lnb2 < 0.f) || !(eps > 0.f)) return false;  // bias corrections divide by 1 - b^t
+  }
+  o.v = v; o.step = step; o.ticket = ticket; o.lr_tab = lr_tab; o.lr_last = lr_tab ? lr_n - 1 : 0;
+  o.b1 = b1; o.b2 = b2; o.omb1 = omb1; o.omb2 = omb2; o.lnb1 = lnb1; o.lnb2 = lnb2; o.eps = eps;
+  return true;
+}
+
+// sl_mlp_sgd's mode 2 under a rule that reads the device-resident optimizer step: from the tiled
+// slab (slab != nullptr: reduction + update in one launch) or from an aggregated gradient
+// (grad_in).  mom is AdamW's first moment, v its second; lr_tab[min(step, lr_n - 1)] is the
+// step's learning rate (nullptr: lr).  The launch advances *step by one (opt_end).
+int sl_mlp_opt(int rule, float* w, float* mom, float* v, const float* slab, int slices, long slab_stride,
+               const float* grad_in, float lr, float mu, float wd, float xa, float xb, uint16_t* w1h,
+               uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, long long* r1p,
+               int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1,
+               float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+  SgdArgs a = {};
+  a.w = w; a.mom = mom; a.slab = slab; a.slices = slices; a.slab_stride = slab_stride;
+  a.grad_in = grad_in; a.n = P_N; a.lr = lr; a.mu = mu; a.wd = wd; a.mode = 2;
+  a.xa = xa; a.xb = xb;
+  a.w1h = w1h; a.w2h = w2h; a.w2th = w2th; a.w3h = w3h; a.w3th = w3th; a.cursor = cursor;
+  a.r1p = r1p; a.stamps = g_sgd_stamps;
+  OptArgs o = {};
+  if (!opt_fill(o, rule, mom, v, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps)) return -1;
+  if (!w || !r1p || (!slab == !grad_in)) return -1;
+  if (slab && ((slab_stride & 3) || slab_stride < TL_STRIDE)) return -1;
+  if (!slab) {
+    if (((uintptr_t)w | (uintptr_t)grad_in | (uintptr_t)(mom ? mom : w)) & 15) return -2;
+    if (rule == RULE_ADAMW)
+      hipLaunchKernelGGL((mlp_opt_update_kernel<false, RULE_ADAMW>), dim3(UPD_TASKS), dim3(UPD_NT), 0, stream, a,
+                         XgArgs{}, o);
+    else
+      hipLaunchKernelGGL((mlp_opt_update_kernel<false, RULE_SGD_LR>), dim3(UPD_TASKS), dim3(UPD_NT), 0, stream, a,
+                         XgArgs{}, o);
+    SL_CHECK_LAUNCH();
+    return 0;
+  }
+  const dim3 grid((sgd_units(true) * SGD_TPG + SGD_NT - 1) / SGD_NT);
+  if (rule == RULE_ADAMW) hipLaunchKernelGGL(mlp_opt_kernel<RULE_ADAMW>, grid, dim3(SGD_NT), 0, stream, a, o);
+  else hipLaunchKernelGGL(mlp_opt_kernel<RULE_SGD_LR>, grid, dim3(SGD_NT), 0, stream, a, o);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
 static bool xg_fill(XgArgs& x, char* const* bases, unsigned* ctl, long slot_bytes, int rank, int world, long chunk4,
                     int inline_sync) {
   if (!bases || !ctl || world < 1 || world > XG_MAX_WORLD || rank < 0 || rank >= world) return false;
@@ -2094,6 +2257,30 @@ int sl_mlp_sgd_xgmi(float* w, float* mom, float lr, float mu, float wd, uint16_t
   if (!xg_fill(x, bases, ctl, slot_bytes, rank, world, chunk4, inline_sync)) return -1;
   const int grid = inline_sync == 2 ? xg_shared_grid(UPD_TASKS, world) : UPD_TASKS;
   hipLaunchKernelGGL(mlp_update_kernel<true>, dim3(grid), dim3(UPD_NT), 0, stream, a, x);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// sl_mlp_sgd_xgmi under a rule that reads the optimizer step (arguments as sl_mlp_opt's)
+int sl_mlp_opt_xgmi(int rule, float* w, float* mom, float* v, float lr, float mu, float wd, uint16_t* w1h,
+                    uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, char* const* bases,
+                    unsigned* ctl, long slot_bytes, int rank, int world, long chunk4, long long* r1p,
+                    int inline_sync, int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1,
+                    float b2, float omb1, float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+  if (!r1p || !w) return -1;
+  if (((uintptr_t)w | (uintptr_t)(mom ? mom : w)) & 15) return -2;
+  SgdArgs a = {};
+  a.w = w; a.mom = mom; a.n = P_N; a.lr = lr; a.mu = mu; a.wd = wd; a.mode = 2;
+  a.w1h = w1h; a.w2h = w2h; a.w2th = w2th; a.w3h = w3h; a.w3th = w3th; a.cursor = cursor; a.r1p = r1p;
+  OptArgs o = {};
+  if (!opt_fill(o, rule, mom, v, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps)) return -1;
+  XgArgs x;
+  if (!xg_fill(x, bases, ctl, slot_bytes, rank, world, chunk4, inline_sync)) return -1;
+  const int grid = inline_sync == 2 ? xg_shared_grid(UPD_TASKS, world) : UPD_TASKS;
+  if (rule == RULE_ADAMW)
+    hipLaunchKernelGGL((mlp_opt_update_kernel<true, RULE_ADAMW>), dim3(grid), dim3(UPD_NT), 0, stream, a, x, o);
+  else
+    hipLaunchKernelGGL((mlp_opt_update_kernel<true, RULE_SGD_LR>), dim3(grid), dim3(UPD_NT), 0, stream, a, x, o);
   SL_CHECK_LAUNCH();
   return 0;
 }

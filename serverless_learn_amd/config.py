@@ -56,6 +56,14 @@ class Config:
     lr: float = 0.05
     momentum: float = 0.9
     weight_decay: float = 0.0
+    optimizer: str = "sgd"             # sgd (momentum SGD) | adamw (beta1, beta2, adam_eps; decoupled weight_decay)
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
+    lr_schedule: str = "constant"      # constant | linear | cosine: what follows the warm-up (ops/optim.py lr_at)
+    lr_warmup_steps: int = 0           # linear warm-up over this many steps (0 = none)
+    lr_decay_steps: int = 0            # step at which the decay ends (0 = max_steps)
+    lr_min_ratio: float = 0.0          # the decay ends at lr_min_ratio * lr
     seed: int = 0
     checkpoint_every: int = 0          # steps between checkpoints (rank 0); 0 = off
     max_steps: int = 0                 # 0 = run until stopped

@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops.optim import OptSpec, adamw_update, lr_at, sgd_update  # noqa: F401  (the rules' semantics live there)
 from ..utils.graphs import GraphSlots
 
 D_IN = 784
@@ -155,13 +156,44 @@ def reference_grads_bf16(flat: torch.Tensor, x_u8: torch.Tensor, y: torch.Tensor
     return losses.sum(), correct, g
 
 
-def sgd_update(flat, mom, grad, lr, momentum, weight_decay):
-    """torch.optim.SGD semantics (dampening 0, no nesterov), in place."""
-    d = grad + weight_decay * flat
-    if mom is not None:
-        mom.mul_(momentum).add_(d)
-        d = mom
-    flat.sub_(lr * d)
+class OptStateCPU:
+    """Optimizer state of the CPU trainers beyond ``params`` / ``mom``: AdamW's second moment
+    ``v`` and the optimizer step ``opt_step`` (a 1-element tensor, so a regroup broadcasts it
+    with the rest), both only where the rule needs them."""
+
+    def _init_opt(self, kw: dict) -> None:
+        self.opt = opt = OptSpec(lr=self.lr, momentum=self.momentum, weight_decay=self.weight_decay, **kw)
+        self.mom = torch.zeros_like(self.params) if (self.momentum > 0 or opt.adamw) else None
+        self.v = torch.zeros_like(self.params) if opt.adamw else None
+        self.opt_step = None if opt.plain else torch.zeros(1, dtype=torch.int32)
+
+    def _opt_update(self, g: torch.Tensor) -> None:
+        if self.opt_step is None:
+            sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
+            return
+        self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]))
+        self.opt_step += 1
+
+    def _opt_state_extra(self, d: dict) -> dict:
+        if self.opt_step is not None:
+            d["opt_step"] = self.opt_step.double().cpu().numpy()
+        if self.v is not None:
+            d["exp_avg_sq"] = self.v[:self.n_params].double().cpu().numpy()
+        return d
+
+    def _opt_load_state_extra(self, d: dict) -> None:
+        if self.opt_step is not None and "opt_step" in d:
+            self.opt_step.fill_(int(d["opt_step"][0]))
+        if self.v is not None and "exp_avg_sq" in d:
+            self.v[:self.n_params].copy_(torch.as_tensor(np.asarray(d["exp_avg_sq"]), dtype=torch.float32))
+
+    def _opt_buffers(self) -> list:
+        return [t for t in (self.v, self.opt_step) if t is not None]
+
+    def reset_optimizer_state(self) -> None:
+        for t in (self.mom, self.v, self.opt_step):
+            if t is not None:
+                t.zero_()
 
 
 @dataclass
@@ -171,17 +203,17 @@ class StepStats:
     samples: int
 
 
-class CPUTrainer:
+class CPUTrainer(OptStateCPU):
     """Plain-torch trainer with the same interface as FusedMLPTrainer (CPU workers)."""
 
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 0.0, seed: int = 0, world_size: int = 1,
-                 flat: torch.Tensor | None = None):
+                 flat: torch.Tensor | None = None, **opt):
         self.batch = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
         self.params = (flat if flat is not None else init_params(seed)).clone().float()
-        self.mom = torch.zeros_like(self.params) if momentum > 0 else None
+        self._init_opt(opt)  # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (OptSpec)
         self.cursor = 0
         self.x = self.y = None
         self.allreduce = None  # callable(tensor) -> None (sum in place)
@@ -216,7 +248,7 @@ class CPUTrainer:
         if self.allreduce is not None:
             self.allreduce(g)
         self.phases.mark("exchange")
-        sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
+        self._opt_update(g)
         self.cursor += 1
         self.phases.mark("update")
         self._last = (float(loss), float(correct))
@@ -241,14 +273,15 @@ class CPUTrainer:
         self.params.copy_(flat.to(self.params))
 
     def state_extra(self) -> dict:
-        return {"cursor": np.array([self.cursor], dtype=np.float64)}
+        return self._opt_state_extra({"cursor": np.array([self.cursor], dtype=np.float64)})
 
     def load_state_extra(self, d: dict) -> None:
         if "cursor" in d:
             self.cursor = int(d["cursor"][0])
+        self._opt_load_state_extra(d)
 
     def buffers(self) -> list:
-        return []
+        return self._opt_buffers()
 
 
 def dh1_scale(grad_scale: float) -> float:
@@ -281,7 +314,7 @@ class FusedMLPTrainer(GraphSlots):
 
     def __init__(self, batch: int, device="cuda", lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 0.0, seed: int = 0, world_size: int = 1,
-                 slices: int | None = None, flat: torch.Tensor | None = None):
+                 slices: int | None = None, flat: torch.Tensor | None = None, **opt):
         from ..ops import _native
 
         if batch % BLOCK_ROWS != 0:
@@ -306,7 +339,20 @@ class FusedMLPTrainer(GraphSlots):
         self.params = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)
         init = flat if flat is not None else init_params(seed)
         self.params[:n].copy_(init.to(dev))
-        self.mom = torch.zeros_like(self.params) if momentum > 0 else None
+        # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
+        self.opt = OptSpec(lr=lr, momentum=momentum, weight_decay=weight_decay, **opt)
+        self.mom = torch.zeros_like(self.params) if (momentum > 0 or self.opt.adamw) else None
+        # AdamW's second moment (mom is its first); the optimizer step the update kernels read
+        # (and its ticket word, mlp_fused.hip opt_end) where the rule depends on the step
+        self.v = torch.zeros_like(self.params) if self.opt.adamw else None
+        self.opt_step = self.opt_ticket = self.lr_tab = None
+        if not self.opt.plain:
+            from ..ops.optim import require_kernels
+
+            require_kernels(self.opt, "sl_mlp_opt", "sl_mlp_opt_xgmi")
+            self.opt_step = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.opt_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._build_lr_table()
         bf = torch.bfloat16
         # W1's shadow is fp16: layer 1 multiplies the exact pixels (fp16 1024 + u) and corrects the
         # offset with the W1 row sums, kept as 64-bit fixed-point partials (mlp_fused.hip, R1_BLK)
@@ -383,11 +429,34 @@ class FusedMLPTrainer(GraphSlots):
     def dw1_coeffs(self) -> tuple:
         return dw1_coeffs(self.xa, self.xb, self.dh1_scale)
 
+    def _build_lr_table(self) -> None:
+        tab = self.opt.lr_table()
+        self.lr_tab = torch.from_numpy(tab).to(self.device) if tab is not None else None
+
+    def set_optimizer(self, **kw) -> None:
+        """Change optimizer hyper-parameters (OptSpec fields) of a step-counter rule: the
+        launches are rebuilt and the captured graphs dropped, as a new ``lr`` does.  The rule
+        itself (which state exists) is fixed at construction."""
+        import dataclasses
+
+        new = dataclasses.replace(self.opt, **kw)
+        if (new.adamw, new.plain) != (self.opt.adamw, self.opt.plain):
+            raise ValueError("the optimizer rule is fixed at construction (build a new trainer)")
+        self.opt = new
+        self.lr, self.momentum, self.weight_decay = new.lr, new.momentum, new.weight_decay
+        if not new.plain:
+            self._build_lr_table()
+        self.graph = None
+        self._lkey = None
+
     def _launches(self):
         """Cached launches for the current buffers/hyper-parameters (rebuilt on change)."""
+        hp = (self.lr, self.momentum, self.weight_decay)
+        if not self.opt.plain and hp != (self.opt.lr, self.opt.momentum, self.opt.weight_decay):
+            self.set_optimizer(lr=hp[0], momentum=hp[1], weight_decay=hp[2])  # an attribute was assigned
         key = (self.x.data_ptr() if self.x is not None else 0, self.n_batches, self.grad_scale, self.lr,
                self.momentum, self.weight_decay, id(self.xgmi), bool(self.xgmi and self.xgmi.two_shot),
-               self.xgmi.inline_sync if self.xgmi is not None else None)
+               self.xgmi.inline_sync if self.xgmi is not None else None, None if self.opt.plain else self.opt)
         if getattr(self, "_lkey", None) == key:
             return self._lc
         n, p = self._n, self._n.ptr
@@ -407,6 +476,12 @@ class FusedMLPTrainer(GraphSlots):
         for name, (mode, from_grad, grad_out, bump) in {"sgd": (2, False, False, True),
                                                         "reduce": (1, False, True, False),
                                                         "update": (2, True, False, True)}.items():
+            if mode == 2 and not self.opt.plain:  # the update under a step-counter rule (reduce: rule-independent)
+                lc[name] = n.Launch("sl_mlp_opt", self.opt.rule, p(self.params), p(self.mom), p(self.v),
+                                    None if from_grad else p(self.slab), self.slices, self.slab_stride,
+                                    p(self.grad) if from_grad else None, self.lr, self.momentum, self.weight_decay,
+                                    *self.dw1_coeffs, *ws, p(self.cursor), p(self.r1p), *self._opt_args())
+                continue
             lc[name] = n.Launch("sl_mlp_sgd", p(self.params), p(self.mom),
                                 None if from_grad else p(self.slab), self.slices, self.slab_stride,
                                 p(self.grad) if from_grad else None, p(self.grad) if grad_out else None,
@@ -418,10 +493,22 @@ class FusedMLPTrainer(GraphSlots):
             lc["xreduce"] = n.Launch("sl_mlp_reduce_xgmi", p(self.slab), self.slices, self.slab_stride, *self.dw1_coeffs,
                                      xg.slot_ptr(0), xg.slot_ptr(1), *xg.args(), xg.inline_sync)
             lc["xbarrier"] = [n.Launch(fn, *xg.args(), *extra) for fn, extra in xg.exchange_launches(self.n_pad)]
-            lc["xupdate"] = n.Launch("sl_mlp_sgd_xgmi", p(self.params), p(self.mom), self.lr, self.momentum,
-                                     self.weight_decay, *ws, p(self.cursor), *xg.args(), p(self.r1p), xg.inline_sync)
+            if self.opt.plain:
+                lc["xupdate"] = n.Launch("sl_mlp_sgd_xgmi", p(self.params), p(self.mom), self.lr, self.momentum,
+                                         self.weight_decay, *ws, p(self.cursor), *xg.args(), p(self.r1p),
+                                         xg.inline_sync)
+            else:
+                lc["xupdate"] = n.Launch("sl_mlp_opt_xgmi", self.opt.rule, p(self.params), p(self.mom), p(self.v),
+                                         self.lr, self.momentum, self.weight_decay, *ws, p(self.cursor), *xg.args(),
+                                         p(self.r1p), xg.inline_sync, *self._opt_args())
         self._lc, self._lkey = lc, key
         return lc
+
+    def _opt_args(self) -> tuple:
+        """Trailing arguments of sl_mlp_opt / sl_mlp_opt_xgmi: step, ticket, lr table, Adam scalars."""
+        p = self._n.ptr
+        return (p(self.opt_step), p(self.opt_ticket), p(self.lr_tab),
+                self.lr_tab.numel() if self.lr_tab is not None else 0, *self.opt.adam_scalars())
 
     def _rows(self, train: bool = True):
         if train:
@@ -622,11 +709,28 @@ class FusedMLPTrainer(GraphSlots):
     def state_extra(self) -> dict:
         """The device batch cursor: a resumed run continues with the batch the saved run
         would have taken next, so save-at-k + resume + m steps equals k + m steps."""
-        return {"cursor": self.cursor.double().cpu().numpy()}
+        d = {"cursor": self.cursor.double().cpu().numpy()}
+        if self.opt_step is not None:  # the optimizer step and AdamW's second moment (the first
+            d["opt_step"] = self.opt_step.double().cpu().numpy()  # travels as the momentum section)
+        if self.v is not None:
+            d["exp_avg_sq"] = self.v[:N_PARAMS].double().cpu().numpy()
+        return d
 
     def load_state_extra(self, d: dict) -> None:
         if "cursor" in d:
             self.cursor.fill_(int(d["cursor"][0]))
+        if self.opt_step is not None:
+            if "opt_step" in d:
+                self.opt_step.fill_(int(d["opt_step"][0]))
+            self.opt_ticket.zero_()
+        if self.v is not None and "exp_avg_sq" in d:
+            self.v[:N_PARAMS].copy_(torch.as_tensor(np.asarray(d["exp_avg_sq"]), dtype=torch.float32))
 
     def buffers(self) -> list:
-        return []
+        """Optimizer state beyond params / mom, broadcast with them after a regroup."""
+        return [t for t in (self.v, self.opt_step) if t is not None]
+
+    def reset_optimizer_state(self) -> None:
+        for t in (self.mom, self.v, self.opt_step, self.opt_ticket):
+            if t is not None:
+                t.zero_()

@@ -28,6 +28,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .mlp import OptStateCPU
+
 ALIGN = 64
 CIFAR_MEAN = (0.4914, 0.4822, 0.4465)
 CIFAR_STD = (0.2470, 0.2435, 0.2616)
@@ -243,12 +245,12 @@ def ref_grads(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, y: torch
     return losses.detach().sum(), correct.detach(), w.grad.detach()
 
 
-class CPUResNetTrainer:
+class CPUResNetTrainer(OptStateCPU):
     """Plain-torch trainer with FusedResNetTrainer's interface (CPU workers, tests)."""
 
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 5e-4,
                  seed: int = 0, world_size: int = 1, stem: str = "cifar", flat: torch.Tensor | None = None,
-                 in_hw: int | None = None):
+                 in_hw: int | None = None, **opt):
         from .mlp import StepStats, sgd_update  # noqa: F401
 
         self.spec = resnet18_spec(stem, 10, in_hw)
@@ -256,7 +258,7 @@ class CPUResNetTrainer:
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
         self.params = (flat if flat is not None else init_params(self.spec, seed)).clone().float()
-        self.mom = torch.zeros_like(self.params) if momentum > 0 else None
+        self._init_opt(opt)  # optimizer=, beta1=, ..., lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
         self.running = running_stats(self.spec)
         self.x = self.y = None
         self.cursor = 0
@@ -290,8 +292,6 @@ class CPUResNetTrainer:
         self.n_batches = self.x.shape[0] // self.batch
 
     def step(self) -> None:
-        from .mlp import sgd_update
-
         b = self.cursor % self.n_batches
         xs = self.x[b * self.batch:(b + 1) * self.batch]
         ys = self.y[b * self.batch:(b + 1) * self.batch]
@@ -301,7 +301,7 @@ class CPUResNetTrainer:
         if self.allreduce is not None:
             self.allreduce(g)
         self.phases.mark("exchange")
-        sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
+        self._opt_update(g)
         self.cursor += 1
         self.phases.mark("update")
         self._last = (float(loss), float(correct))
@@ -333,7 +333,7 @@ class CPUResNetTrainer:
         for name, (rm, rv) in self.running.items():
             d[f"bn/{name}/mean"] = rm.double().numpy()
             d[f"bn/{name}/var"] = rv.double().numpy()
-        return d
+        return self._opt_state_extra(d)
 
     def load_state_extra(self, d: dict) -> None:
         if "cursor" in d:
@@ -342,10 +342,11 @@ class CPUResNetTrainer:
             if f"bn/{name}/mean" in d:
                 rm.copy_(torch.from_numpy(np.asarray(d[f"bn/{name}/mean"])).to(rm.dtype))
                 rv.copy_(torch.from_numpy(np.asarray(d[f"bn/{name}/var"])).to(rv.dtype))
+        self._opt_load_state_extra(d)
 
     def buffers(self) -> list:
         """Non-parameter state every replica must agree on (broadcast after a regroup)."""
-        return [t for pair in self.running.values() for t in pair]
+        return [t for pair in self.running.values() for t in pair] + self._opt_buffers()
 
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor):
         """Inference with the BatchNorm running statistics (eval mode)."""

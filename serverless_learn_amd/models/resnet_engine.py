@@ -78,7 +78,7 @@ class FusedResNetTrainer(GraphSlots):
     def __init__(self, batch: int, device="cuda", lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 5e-4, seed: int = 0, world_size: int = 1, stem: str = "cifar",
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
-                 in_hw: int | None = None):
+                 in_hw: int | None = None, **opt):
         from ..ops import _native
         from ..ops import cnn as K
         from ..ops import optim as O
@@ -100,7 +100,18 @@ class FusedResNetTrainer(GraphSlots):
         n = spec.n_flat
         self.params = torch.zeros(n, dtype=torch.float32, device=dev)
         self.params.copy_((flat if flat is not None else init_params(spec, seed)).to(dev))
-        self.mom = torch.zeros_like(self.params) if momentum > 0 else None
+        # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
+        self.opt = O.OptSpec(lr=lr, momentum=momentum, weight_decay=weight_decay, **opt)
+        self.mom = torch.zeros_like(self.params) if (momentum > 0 or self.opt.adamw) else None
+        # AdamW's second moment (mom is its first) and the device-resident optimizer step the
+        # update kernel reads, where the rule depends on the step
+        self.v = torch.zeros_like(self.params) if self.opt.adamw else None
+        self.opt_step = self.lr_tab = None
+        if not self.opt.plain:
+            O.require_kernels(self.opt, "sl_adamw_flat", "sl_sgd_flat_lr")
+            self.opt_step = torch.zeros(1, dtype=torch.int32, device=dev)
+            tab = self.opt.lr_table()
+            self.lr_tab = torch.from_numpy(tab).to(dev) if tab is not None else None
         self.grad = torch.zeros_like(self.params)
         self.shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
         bns = list(spec.bns())
@@ -421,11 +432,25 @@ class FusedResNetTrainer(GraphSlots):
         if self.allreduce is not None:
             self.allreduce(self.grad)
         self.phases.mark("exchange")
-        self.O.sgd_flat(self.params, self.grad, self.mom, self.lr, self.momentum, self.weight_decay,
-                        shadow=self.shadow)
+        self._update()
         self.wt()
         self.K.cursor_bump(self.cursor)
         self.phases.mark("update")
+
+    def _update(self) -> None:
+        """The optimizer launch (the step-counter rules: plus the bump of the optimizer step)."""
+        O = self.O
+        if self.opt_step is None:
+            O.sgd_flat(self.params, self.grad, self.mom, self.lr, self.momentum, self.weight_decay,
+                       shadow=self.shadow)
+            return
+        if self.opt.adamw:
+            O.adamw_flat(self.params, self.grad, self.mom, self.v, self.opt_step, self.opt, self.lr_tab,
+                         shadow=self.shadow)
+        else:
+            O.sgd_flat_lr(self.params, self.grad, self.mom, self.opt_step, self.lr_tab, self.momentum,
+                          self.weight_decay, shadow=self.shadow)
+        self.K.cursor_bump(self.opt_step)
 
     def step(self) -> None:
         if self.graph is not None:
@@ -491,6 +516,10 @@ class FusedResNetTrainer(GraphSlots):
         for name, b in self.bn.items():
             d[f"bn/{name}/mean"] = b.run_mean.double().cpu().numpy()
             d[f"bn/{name}/var"] = b.run_var.double().cpu().numpy()
+        if self.opt_step is not None:  # the optimizer step and AdamW's second moment (the first
+            d["opt_step"] = self.opt_step.double().cpu().numpy()  # travels as the momentum section)
+        if self.v is not None:
+            d["exp_avg_sq"] = self.v.double().cpu().numpy()
         return d
 
     def load_state_extra(self, d: dict) -> None:
@@ -500,11 +529,21 @@ class FusedResNetTrainer(GraphSlots):
             if f"bn/{name}/mean" in d:
                 b.run_mean.copy_(torch.as_tensor(d[f"bn/{name}/mean"], dtype=torch.float32))
                 b.run_var.copy_(torch.as_tensor(d[f"bn/{name}/var"], dtype=torch.float32))
+        if self.opt_step is not None and "opt_step" in d:
+            self.opt_step.fill_(int(d["opt_step"][0]))
+        if self.v is not None and "exp_avg_sq" in d:
+            self.v.copy_(torch.as_tensor(d["exp_avg_sq"], dtype=torch.float32))
 
     def buffers(self) -> list:
         """BN running statistics: broadcast with the parameters after a regroup, so every
         replica evaluates identically (each rank's statistics come from its own batches)."""
-        return [t for b in self.bn.values() for t in (b.run_mean, b.run_var)]
+        bufs = [t for b in self.bn.values() for t in (b.run_mean, b.run_var)]
+        return bufs + [t for t in (self.v, self.opt_step) if t is not None]
+
+    def reset_optimizer_state(self) -> None:
+        for t in (self.mom, self.v, self.opt_step):
+            if t is not None:
+                t.zero_()
 
     # ---- inference with running statistics ----
     def _eval_coef(self, bn: _BN, eps: float = 1e-5) -> torch.Tensor:

@@ -1,22 +1,211 @@
-"""K5: flat fused SGD (one launch for a whole model's parameter vector)."""
+"""K5: the optimizer.  The update rules' semantics in one place (float64 reference functions
+the CPU trainers run and the GPU tests compare against), the hyper-parameter bundle every
+trainer shares, and the flat fused update kernels (one launch for a whole model's vector).
+
+Two rules: momentum SGD (``torch.optim.SGD``, dampening 0, no nesterov) and AdamW
+(``torch.optim.AdamW``: decoupled weight decay, bias correction, no amsgrad).  Both take their
+learning rate from :func:`lr_at`: linear warm-up, then constant, linear or cosine decay.  On the
+GPU the step number is a device-resident counter, so a captured graph replays with a moving
+learning rate; the schedule reaches the kernels as an fp32 table of ``lr_at`` values.
+"""
 from __future__ import annotations
 
+import math
+from dataclasses import dataclass
+
+import numpy as np
 import torch
 
 from . import _native as N
 
+OPTIMIZERS = ("sgd", "adamw")
+SCHEDULES = ("constant", "linear", "cosine")
+
+# update-kernel rules (csrc/kernels/mlp_fused.hip)
+RULE_SGD, RULE_SGD_LR, RULE_ADAMW = 0, 1, 2
+
 N.register("sl_sgd_flat", [N.P, N.P, N.P, N.P, N.L, N.F, N.F, N.F, N.F, N.P])
 N.register("sl_to_bf16", [N.P, N.P, N.L, N.P])
+_ADAM = [N.F] * 7  # beta1, beta2, 1 - beta1, 1 - beta2, ln beta1, ln beta2, eps
+N.register("sl_adamw_flat", [N.P, N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, N.F, *_ADAM, N.P])
+N.register("sl_sgd_flat_lr", [N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, N.F, N.P])
+_STEP = [N.P, N.P, N.P, N.I]  # step, ticket, lr table, its length
+N.register("sl_mlp_opt", [N.I, N.P, N.P, N.P, N.P, N.I, N.L, N.P, N.F, N.F, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P,
+                          N.P, N.P, *_STEP, *_ADAM, N.P])
+N.register("sl_mlp_opt_xgmi", [N.I, N.P, N.P, N.P, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.L, N.I,
+                               N.I, N.L, N.P, N.I, *_STEP, *_ADAM, N.P])
 
 
-def sgd_flat(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor | None, lr: float, momentum: float = 0.0,
-             weight_decay: float = 0.0, shadow: torch.Tensor | None = None, grad_scale: float = 1.0) -> None:
+# ---- semantics ----
+def lr_at(step: int, lr: float, schedule: str = "constant", warmup_steps: int = 0, decay_steps: int = 0,
+          min_ratio: float = 0.0) -> float:
+    """Learning rate of 0-based ``step`` (the number of updates already applied), in float64.
+
+    ``step < warmup_steps``: ``lr (step + 1) / warmup_steps``.  After that, with
+    ``p = min(1, (step - warmup_steps) / max(1, decay_steps - warmup_steps))`` and
+    ``r = min_ratio``: ``constant`` 1, ``linear`` ``r + (1 - r)(1 - p)``, ``cosine``
+    ``r + (1 - r) (1 + cos(pi p)) / 2``; past ``decay_steps`` it stays at ``r lr``."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"unknown lr_schedule {schedule!r} (choose from {SCHEDULES})")
+    step, warmup_steps, decay_steps = int(step), int(warmup_steps), int(decay_steps)
+    if schedule != "constant" and decay_steps <= 0:
+        raise ValueError(f"lr_schedule {schedule!r} needs lr_decay_steps > 0 (or max_steps, which it defaults to)")
+    if step < warmup_steps:
+        return float(lr) * (step + 1) / warmup_steps
+    if schedule == "constant":
+        return float(lr)
+    p = min(1.0, (step - warmup_steps) / max(1, decay_steps - warmup_steps))
+    r = float(min_ratio)
+    shape = 1.0 - p if schedule == "linear" else 0.5 * (1.0 + math.cos(math.pi * p))
+    return float(lr) * (r + (1.0 - r) * shape)
+
+
+def sgd_update(flat, mom, grad, lr, momentum, weight_decay):
+    """torch.optim.SGD semantics (dampening 0, no nesterov), in place."""
+    d = grad + weight_decay * flat
+    if mom is not None:
+        mom.mul_(momentum).add_(d)
+        d = mom
+    flat.sub_(lr * d)
+
+
+def adamw_update(flat, m, v, grad, lr_t, beta1, beta2, eps, weight_decay, t):
+    """torch.optim.AdamW semantics (no amsgrad), in place; ``t`` = step + 1."""
+    flat.mul_(1.0 - lr_t * weight_decay)
+    m.mul_(beta1).add_(grad, alpha=1.0 - beta1)
+    v.mul_(beta2).addcmul_(grad, grad, value=1.0 - beta2)
+    denom = v.sqrt().div_(math.sqrt(1.0 - beta2 ** t)).add_(eps)
+    flat.addcdiv_(m, denom, value=-lr_t / (1.0 - beta1 ** t))
+
+
+@dataclass(frozen=True)
+class OptSpec:
+    """The optimizer hyper-parameters a trainer is built with (its keyword arguments)."""
+    lr: float = 0.05
+    momentum: float = 0.9
+    weight_decay: float = 0.0
+    optimizer: str = "sgd"
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
+    lr_schedule: str = "constant"
+    lr_warmup_steps: int = 0
+    lr_decay_steps: int = 0
+    lr_min_ratio: float = 0.0
+
+    def __post_init__(self):
+        if self.optimizer not in OPTIMIZERS:
+            raise ValueError(f"unknown optimizer {self.optimizer!r} (choose from {OPTIMIZERS})")
+        if self.lr_schedule not in SCHEDULES:
+            raise ValueError(f"unknown lr_schedule {self.lr_schedule!r} (choose from {SCHEDULES})")
+        if self.lr_warmup_steps < 0 or self.lr_decay_steps < 0:
+            raise ValueError("lr_warmup_steps and lr_decay_steps must be >= 0")
+        if self.lr_schedule != "constant" and self.lr_decay_steps <= 0:
+            raise ValueError(f"lr_schedule {self.lr_schedule!r} needs lr_decay_steps > 0 "
+                             "(the worker defaults it to max_steps)")
+        if self.adamw and not (0.0 < self.beta1 < 1.0 and 0.0 < self.beta2 < 1.0 and self.adam_eps > 0.0):
+            raise ValueError("adamw needs 0 < beta1, beta2 < 1 and adam_eps > 0")
+
+    @property
+    def adamw(self) -> bool:
+        return self.optimizer == "adamw"
+
+    @property
+    def scheduled(self) -> bool:
+        return self.lr_schedule != "constant" or self.lr_warmup_steps > 0
+
+    @property
+    def plain(self) -> bool:
+        """Momentum SGD at a fixed lr: the rule without a step counter."""
+        return not self.adamw and not self.scheduled
+
+    @property
+    def rule(self) -> int:
+        return RULE_ADAMW if self.adamw else RULE_SGD_LR if self.scheduled else RULE_SGD
+
+    def lr_at(self, step: int) -> float:
+        return lr_at(step, self.lr, self.lr_schedule, self.lr_warmup_steps, self.lr_decay_steps, self.lr_min_ratio)
+
+    def lr_table(self) -> np.ndarray | None:
+        """fp32 ``lr_at`` of steps 0 .. last, where every later step has the last one's value
+        (the kernels index it with ``min(step, last)``); None at a fixed lr."""
+        if not self.scheduled:
+            return None
+        last = self.lr_warmup_steps
+        if self.lr_schedule != "constant":
+            last = max(self.lr_decay_steps, self.lr_warmup_steps + 1)
+        return np.array([self.lr_at(s) for s in range(last + 1)], dtype=np.float32)
+
+    def adam_scalars(self) -> tuple:
+        """The kernels' beta-derived scalars, each computed in double and rounded once (fp32
+        ``1 - 0.999`` is 3e-5 off; ``1 - beta^t`` is ``-expm1(t ln beta)`` on the device)."""
+        if not self.adamw:
+            return (0.0,) * 7
+        return (self.beta1, self.beta2, 1.0 - self.beta1, 1.0 - self.beta2, math.log(self.beta1),
+                math.log(self.beta2), self.adam_eps)
+
+    def update(self, flat, mom, v, grad, step: int) -> None:
+        """One reference update of 0-based ``step``, in place (the CPU trainers' optimizer)."""
+        if self.adamw:
+            adamw_update(flat, mom, v, grad, self.lr_at(step), self.beta1, self.beta2, self.adam_eps,
+                         self.weight_decay, step + 1)
+        else:
+            sgd_update(flat, mom, grad, self.lr_at(step), self.momentum, self.weight_decay)
+
+    def meta(self) -> dict:
+        """Checkpoint metadata (``meta["optimizer"]``)."""
+        d = {"lr": self.lr, "momentum": self.momentum}
+        if not self.plain:
+            d.update(name=self.optimizer, beta1=self.beta1, beta2=self.beta2, eps=self.adam_eps,
+                     weight_decay=self.weight_decay, schedule=self.lr_schedule, warmup_steps=self.lr_warmup_steps,
+                     decay_steps=self.lr_decay_steps, min_ratio=self.lr_min_ratio)
+        return d
+
+
+def require_kernels(spec: OptSpec, *names: str) -> None:
+    """The step-counter rules need their entry points: an older kernel build (kept for A/B
+    runs of the SGD path) does not have them, and there is no fallback."""
+    lib = N.lib()
+    missing = [n for n in names if not hasattr(lib, n)]
+    if missing:
+        raise RuntimeError(f"optimizer {spec.optimizer!r} / lr_schedule {spec.lr_schedule!r} need "
+                           f"{', '.join(missing)}: not in this kernel library")
+
+
+# ---- flat kernels ----
+def _check_flat(w, g, shadow):
     assert w.is_cuda and w.dtype == torch.float32 and g.dtype == torch.float32
     assert w.is_contiguous() and g.is_contiguous() and g.numel() == w.numel()
     if shadow is not None:
         assert shadow.dtype == torch.bfloat16 and shadow.numel() == w.numel()
+
+
+def sgd_flat(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor | None, lr: float, momentum: float = 0.0,
+             weight_decay: float = 0.0, shadow: torch.Tensor | None = None, grad_scale: float = 1.0) -> None:
+    _check_flat(w, g, shadow)
     N.call("sl_sgd_flat", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), float(lr), float(momentum),
            float(weight_decay), float(grad_scale), N.stream_ptr())
+
+
+def sgd_flat_lr(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor | None, step: torch.Tensor,
+                lr_tab: torch.Tensor, momentum: float = 0.0, weight_decay: float = 0.0,
+                shadow: torch.Tensor | None = None, grad_scale: float = 1.0) -> None:
+    """sgd_flat at the learning rate ``lr_tab[min(step, len - 1)]`` (``step``: int32 on the device)."""
+    _check_flat(w, g, shadow)
+    assert step.dtype == torch.int32 and lr_tab.dtype == torch.float32
+    N.call("sl_sgd_flat_lr", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), N.ptr(step), N.ptr(lr_tab),
+           lr_tab.numel(), float(momentum), float(weight_decay), float(grad_scale), N.stream_ptr())
+
+
+def adamw_flat(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor,
+               spec: OptSpec, lr_tab: torch.Tensor | None = None, shadow: torch.Tensor | None = None,
+               grad_scale: float = 1.0) -> None:
+    """One AdamW update of step ``step`` (int32 on the device; the caller advances it)."""
+    _check_flat(w, g, shadow)
+    assert step.dtype == torch.int32 and m.numel() == w.numel() and v.numel() == w.numel()
+    N.call("sl_adamw_flat", N.ptr(w), N.ptr(g), N.ptr(m), N.ptr(v), N.ptr(shadow), w.numel(), N.ptr(step),
+           N.ptr(lr_tab), lr_tab.numel() if lr_tab is not None else 0, float(spec.lr), float(spec.weight_decay),
+           float(grad_scale), *spec.adam_scalars(), N.stream_ptr())
 
 
 def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:

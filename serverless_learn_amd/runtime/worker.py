@@ -142,6 +142,12 @@ class Worker:
         world = max(1, self.view["world"]) if self.cfg.sync == "allreduce" else 1
         kw = dict(batch=self.cfg.batch, lr=self.cfg.lr, momentum=self.cfg.momentum,
                   weight_decay=self.cfg.weight_decay, seed=self.cfg.seed, world_size=world)
+        c = self.cfg
+        if (c.optimizer, c.lr_schedule, c.lr_warmup_steps) != ("sgd", "constant", 0):
+            # (unknown names and a decay without a horizon are refused by the trainer, ops/optim.py OptSpec)
+            kw.update(optimizer=c.optimizer, beta1=c.beta1, beta2=c.beta2, adam_eps=c.adam_eps,
+                      lr_schedule=c.lr_schedule, lr_warmup_steps=c.lr_warmup_steps,
+                      lr_decay_steps=c.lr_decay_steps or c.max_steps, lr_min_ratio=c.lr_min_ratio)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
@@ -278,10 +284,19 @@ class Worker:
                 self.log.info("checkpoint_skipped", ckpt_step=meta.get("step"), step=self.step)
                 return
             self.trainer.set_flat(torch.from_numpy(params))
+            # a checkpoint written under another optimizer: parameters, cursor and BN statistics
+            # load, the optimizer state starts from zero (SGD's momentum is not Adam's first
+            # moment, nor the reverse); without a name it is SGD's
+            ck_opt = (meta.get("optimizer") or {}).get("name", "sgd")
+            if ck_opt != self.cfg.optimizer:
+                self.log.warn("checkpoint_optimizer_mismatch", ckpt=ck_opt, running=self.cfg.optimizer)
+                mom = None
+                extra = {k: v for k, v in extra.items() if k not in ("opt_step", "exp_avg_sq")}
+                self.trainer.reset_optimizer_state()
             if mom is not None and self.trainer.mom is not None:
                 self.trainer.mom[:self.trainer.n_params].copy_(torch.from_numpy(mom))
             if extra and hasattr(self.trainer, "load_state_extra"):
-                self.trainer.load_state_extra(extra)  # batch cursor, BN running statistics
+                self.trainer.load_state_extra(extra)  # batch cursor, BN running statistics, optimizer step, v
             self.trainer.graph = None  # a captured graph holds the old state's launches
             self.step = int(meta.get("step", 0))
             self.resumed_step = self.step
@@ -296,7 +311,7 @@ class Worker:
             mom = self.trainer.mom[:n].cpu().numpy() if self.trainer.mom is not None else None
             meta = {"model": self.trainer.model_name, "step": self.step, "epoch": self.group.epoch,
                     "layout": self.trainer.layout(),
-                    "optimizer": {"lr": self.cfg.lr, "momentum": self.cfg.momentum}}
+                    "optimizer": self.trainer.opt.meta()}
             extra = self.trainer.state_extra() if hasattr(self.trainer, "state_extra") else {}
         data = ckfmt.encode(flat, meta, mom, extra)
         file_num = ckfmt.CKPT_BASE + self.ckpt_slot
