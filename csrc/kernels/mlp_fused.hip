@@ -45,7 +45,7 @@ namespace {
 // Cache policy of the stores that hand a kernel's outputs to the next launch: 16 = sc1
 // (write-through), 0 = default write-back (kept: write-through halves the launch gaps but
 // stretches the kernels by more, profiles/r05_sc1).  OUT_AUX: whole-line 16-B stores (H1 / dH2 rows,
-// weight-gradient slabs); OUT_AUX_NARROW: the partial-line ones (dH1's 8-B fragment rows, the
+// weight-gradient slabs); OUT_AUX_NARROW: the partial-line ones (dH1's 16-B fragment rows, the
 // w3p partials' 4-B stores).
 #ifndef SL_STORE_AUX
 #define SL_STORE_AUX 0
@@ -146,6 +146,25 @@ struct FragSrc {
     return __builtin_bit_cast(short8_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (n * ks_per_row + ks) * 1024, 0));
   }
 };
+// The same blocks read with a permuted lane -> slot map, for an output whose accumulators go
+// straight to row-major memory: of the fragment pair (2j, 2j+1) -- matrix rows 32 j .. 32 j + 31
+// from nt0 -- the lane at (k-group g, MFMA row r) takes row 32 j + 8 (r >> 2) + (r & 3) for the
+// even fragment and 4 rows further for the odd one.  With the weights as the first MFMA operand,
+// lane (lg, lr) then holds rows 32 j + 8 lg .. + 3 (even) and + 4 .. + 7 (odd) of column lr:
+// 8 consecutive output features of one batch row, one 16-B store.  Each wave-load is still 64
+// 16-B pieces, half of each of two neighbouring 1 KB blocks; the K sums are unchanged.
+struct FragSrcPair {
+  __amdgpu_buffer_rsrc_t rs;
+  int voff;
+  __device__ __forceinline__ FragSrcPair(const uint16_t* w, int bytes, int nt0, int ks_per_row, int lane)
+      : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(w), 0, bytes, 0x00020000)),
+        voff(((nt0 + ((lane >> 3) & 1)) * ks_per_row * 512 + ((lane >> 4) * 16 + ((lane >> 2) & 1) * 8 + (lane & 3)) * 8) * 2) {}
+  // fragment n of the permuted pair n / 2, k-step ks
+  __device__ __forceinline__ short8_t operator()(int n, int ks, int ks_per_row) const {
+    return __builtin_bit_cast(
+        short8_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, ((n & ~1) * ks_per_row + ks) * 1024 + (n & 1) * 64, 0));
+  }
+};
 
 // diagnostics: per-workgroup row-kernel stamps [0..9 phases (s_memtime) | 10 HW_ID | 11 XCC_ID |
 // 12..15 sub-phases | 16, 17 start / end s_memrealtime (100 MHz): their ratio gives the shader clock]
@@ -155,9 +174,6 @@ constexpr int ROW_STAMPS = 20;
 // 0: off (age decides: the older workgroup wins issue, finishes ~25k cycles earlier and the
 // younger runs its tail alone); 1 (default): the younger raises its priority after layer 1 and
 // the pair ends together (driver form +2.3 %, profiles/r05_prio); 2: after the softmax (neutral).
-#ifndef SL_ROWS_B3PF
-#define SL_ROWS_B3PF 1  // rows kernel: layer-3 bias prefetched with the labels
-#endif
 #ifndef SL_ROWS_PRO_LATE
 #define SL_ROWS_PRO_LATE 1  // rows kernel (128-row tile): bias prologue after the stream's first loads
 #endif
@@ -267,30 +283,12 @@ __device__ __forceinline__ void copy_out_f16(const uint16_t* src, int ld, uint16
   }
 }
 
-// Reductions over a DPP row (16 lanes): xor 1 and xor 2 by quad_perm, then
-// row_half_mirror (i -> 7 - i) and row_mirror (i -> 15 - i) pair the halves.
+// Exchanges within a DPP row (16 lanes): xor 1 and xor 2 by quad_perm (0xB1, 0x4E),
+// row_half_mirror (0x141, i -> 7 - i) and row_mirror (0x140, i -> 15 - i) pair the halves.
 template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  return fmaxf(v, dpp_f<0x140>(v));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  return v + dpp_f<0x140>(v);
-}
-__device__ __forceinline__ int row16_min(int v) {
-  v = min(v, dpp_i<0xB1>(v));
-  v = min(v, dpp_i<0x4E>(v));
-  v = min(v, dpp_i<0x141>(v));
-  return min(v, dpp_i<0x140>(v));
-}
 
 // One of the 8 iterations of copy_out (per-thread share 1/8): lets the
 // activation stores be spread over the NEXT layer's k-loop.  A burst of 64 KB
@@ -458,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
       for (int n = 0; n < NF; ++n) acc[m][n] = mfma16(b[n], af[m], acc[m][n]);
   };
   // one 256-deep layer (K = 256, A = an activation image, B = a fragment-ordered weight)
-  auto k256 = [&](const FragSrc& fw, const uint16_t* ha, auto&& after) {
+  auto k256 = [&](const auto& fw, const uint16_t* ha, auto&& after) {
     if constexpr (APF) {
       kloop_ring_a<KS2, NF, MF, RING>(
           [&](short8_t (&r)[NF], int st) {
@@ -563,20 +561,21 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   const int wcol = NF * wng;
   const FragSrc f_w1(a.w1h, HID * D_INP * 2, wcol, KS1, lane);
   const FragSrc f_w2(a.w2h, HID * HID * 2, wcol, KS2, lane);
-  const FragSrc f_w2t(a.w2th, HID * HID * 2, wcol, KS2, lane);
+  // the 128-row tile's dH1 leaves the accumulators as 16-B row pieces: permuted fragment pairs
+  const std::conditional_t<BIG, FragSrcPair, FragSrc> f_w2t(a.w2th, HID * HID * 2, wcol, KS2, lane);
   const FragSrc f_w3(a.w3h, 16 * HID * 2, 0, KS2, lane);
   const FragSrc f_w3t(a.w3th, HID * 32 * 2, NF * wng, 1, lane);
 
-  // labels of this lane's 4 softmax rows ((sp * NWV + wave) * 16 + 4 lg + r), fetched long before use
-  uint32_t lab4[SPW];
+  // label of this lane's softmax row ((sp * NWV + wave) * 16 + lr), fetched long before use
+  uint32_t lab1[SPW];
 #pragma unroll
-  for (int sp = 0; sp < SPW; ++sp)
-    lab4[sp] = a.y ? *reinterpret_cast<const uint32_t*>(a.y + srow0 + (sp * NWV + wave) * 16 + 4 * lg) : 0u;
-#if SL_ROWS_B3PF
-  // layer 3's bias for this lane's logit column, fetched here instead of at the softmax (an
-  // index clamp, not a condition: the load is unconditional, the column mask is applied at use)
-  const float b3pf = a.b3[lr < NC ? lr : NC - 1];
-#endif
+  for (int sp = 0; sp < SPW; ++sp) lab1[sp] = a.y ? a.y[srow0 + (sp * NWV + wave) * 16 + lr] : 0u;
+  // layer 3's bias for this lane's 4 logit columns (classes 4 lg .. 4 lg + 3), fetched here
+  // instead of at the softmax (an index clamp, not a condition: the loads are unconditional,
+  // the column mask is applied at use)
+  float b3pf[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) b3pf[r] = a.b3[4 * lg + r < NC ? 4 * lg + r : NC - 1];
 
   {
   zero_acc();
@@ -803,9 +802,12 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   stamp(4);
 
   // ---- layer 3 + softmax cross-entropy: wave w owns rows 16w..16w+15; dZ -> RZ ----
-  // Row reductions over the 16 lanes holding one row's logits run on DPP
-  // (quad perms + row half-mirror + row mirror), not ds_bpermute shuffles whose
-  // LDS round trips made this phase ~10k cycles; W3 and labels were prefetched.
+  // Operands swapped as in every other layer (weights first): lane (lg, lr) holds classes
+  // 4 lg .. 4 lg + 3 of ONE row (rb + lr), so a row quantity is 3 in-lane operations plus the
+  // xor-16 and xor-32 partners (the four lane quarters), and one instruction stream serves 16
+  // rows.  (With rows in the lane's registers every reduction was a 4-step DPP chain over 16
+  // lanes, once per register: ~21 VALU per batch row.)  The sums keep the binary tree of that
+  // form -- quads of classes, pairs of quads, then classes 0-7 + 8-15 -- and with it their bits.
   floatx4_t z3[SPW];  // the passes' logits first: their MFMA chains interleave
 #pragma unroll
   for (int sp = 0; sp < SPW; ++sp) z3[sp] = zero4();
@@ -813,39 +815,58 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   for (int ks = 0; ks < KS2; ++ks)
 #pragma unroll
     for (int sp = 0; sp < SPW; ++sp)
-      z3[sp] = mfma16(lds8(R0 + ((sp * NWV + wave) * 16 + lr) * HS_LD + 8 * lg + ks * 32), w3f[ks], z3[sp]);
+      z3[sp] = mfma16(w3f[ks], lds8(R0 + ((sp * NWV + wave) * 16 + lr) * HS_LD + 8 * lg + ks * 32), z3[sp]);
+  auto quarters_max = [](float v) {
+    v = fmaxf(v, __shfl_xor(v, 16));
+    return fmaxf(v, __shfl_xor(v, 32));
+  };
+  auto quarters_sum = [](float v) {
+    v += __shfl_xor(v, 16);
+    return v + __shfl_xor(v, 32);
+  };
+  auto quarters_min = [](int v) {
+    v = min(v, __shfl_xor(v, 16));
+    return min(v, __shfl_xor(v, 32));
+  };
 #pragma unroll
   for (int sp = 0; sp < SPW; ++sp) {
-    const int rb = (sp * NWV + wave) * 16;  // this pass's 16 rows
-    const floatx4_t z = z3[sp];
-    const int c = lr;
-#if SL_ROWS_B3PF
-    const float bias3 = c < NC ? b3pf : 0.f;
-#else
-    const float bias3 = c < NC ? a.b3[c] : 0.f;
-#endif
+    const int row = (sp * NWV + wave) * 16 + lr;  // this lane's row of the pass's 16
+    int lab = (int)lab1[sp];
+    lab = lab < NC ? lab : 0;
+    float zz[4], e[4], zs[4];
+    int ix[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) zz[r] = 4 * lg + r < NC ? z3[sp][r] + b3pf[r] : -INFINITY;
+    const float mx = quarters_max(fmaxf(fmaxf(zz[0], zz[1]), fmaxf(zz[2], zz[3])));
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = rb + 4 * lg + r;
-      const float zz = c < NC ? z[r] + bias3 : -INFINITY;
-      const float mx = row16_max(zz);
-      const float e = c < NC ? __expf(zz - mx) : 0.f;
-      int lab = (int)((lab4[sp] >> (8 * r)) & 0xffu);
-      lab = lab < NC ? lab : 0;
-      const float s = row16_sum(e);
-      const float zl = row16_sum(c == lab ? zz : 0.f);
-      const int idx = row16_min((zz == mx) ? c : 16);
-      const float lse = mx + __logf(s);
-      if (c == 0) {
-        if (a.loss) a.loss[row0 + row] = lse - zl;
-        if (a.correct) a.correct[row0 + row] = (idx == lab) ? 1.f : 0.f;
+      const int c = 4 * lg + r;
+      e[r] = c < NC ? __expf(zz[r] - mx) : 0.f;
+      zs[r] = c == lab ? zz[r] : 0.f;
+      ix[r] = (zz[r] == mx) ? c : 16;
+    }
+    const float s = quarters_sum((e[0] + e[1]) + (e[2] + e[3]));
+    const float zl = quarters_sum((zs[0] + zs[1]) + (zs[2] + zs[3]));
+    const int idx = quarters_min(min(min(ix[0], ix[1]), min(ix[2], ix[3])));
+    const float lse = mx + __logf(s);
+    if (lg == 0) {  // 16 consecutive rows per store instruction
+      if (a.loss) a.loss[row0 + row] = lse - zl;
+      if (a.correct) a.correct[row0 + row] = (idx == lab) ? 1.f : 0.f;
+    }
+    if (a.logits) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (4 * lg + r < NC) a.logits[(long)(row0 + row) * NC + 4 * lg + r] = zz[r];
+    }
+    if (TRAIN) {
+      float dz[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = 4 * lg + r;
+        dz[r] = c < NC ? (e[r] / s - (c == lab ? 1.f : 0.f)) * a.grad_scale : 0.f;
       }
-      if (a.logits && c < NC) a.logits[(long)(row0 + row) * NC + c] = zz;
-      if (TRAIN) {
-        const float dzv = c < NC ? (e / s - (c == lab ? 1.f : 0.f)) * a.grad_scale : 0.f;
-        RZ[row * DZL + c] = f2bf(dzv);
-        if constexpr (DZL > 16) RZ[row * DZL + 16 + c] = 0;
-      }
+      *reinterpret_cast<uint2*>(RZ + row * DZL + 4 * lg) = make_uint2(pack2(dz[0], dz[1]), pack2(dz[2], dz[3]));
+      if constexpr (DZL > 16) *reinterpret_cast<uint2*>(RZ + row * DZL + 16 + 4 * lg) = make_uint2(0u, 0u);
     }
   }
   if (!TRAIN) return;
@@ -947,49 +968,70 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   stamp(8);
   if constexpr (BIG) {
     // dH1 straight from the accumulators: mask (H1 nibbles), fp16 of dH1 * dh1_scale to
-    // HBM (8 B per fragment row), and the db1 partial as fp32 column sums (DPP over the
-    // 16 rows of a fragment).  The LDS image + barrier + re-read of the other tiles cost
-    // ~16k cycles here with every CU in this phase at once (profiles/r03_big).
-    int mbo = (rw + lr) * 64 + (cw >> 2) + lg;
+    // HBM, and the db1 partial as fp32 column sums (DPP over the 16 rows of a fragment).
+    // The LDS image + barrier + re-read of the other tiles cost ~16k cycles here with every
+    // CU in this phase at once (profiles/r03_big).
+    // f_w2t's permuted pairs: acc[m][2j] and acc[m][2j+1] are features cw + 32 j + 8 lg .. + 7
+    // of row m * 16 + lr -- two neighbouring mask bytes (one 16-bit read) and one 16-B store
+    // (8-B stores of 4 columns per fragment were store-issue bound).  No cross-lane exchange.
+    // (A permlane16 swap of fragment pairs, cdna_hip_programming.md T21, gave exact one-step
+    // gradients but made multi-step training diverge non-deterministically, profiles/r03_big:
+    // the same symptom as the store hazard padded below, which that form did not pad.)
+    int mbo = (rw + lr) * 64 + (cw >> 2) + 2 * lg;
     asm volatile("" : "+v"(mbo));
     const uint8_t* M1b = M1 + mbo;
     const auto dst = __builtin_amdgcn_make_buffer_rsrc(a.dh1 + (long)row0 * HID, 0, BM * HID * 2, 0x00020000);
-    // 8-B stores of this lane's 4 columns per fragment.  A 16-B form (permlane16 swap of
-    // fragment pairs, cdna_hip_programming.md T21) gave exact one-step gradients but made
-    // multi-step training diverge non-deterministically, even with s_nop around the swap
-    // (profiles/r03_big); it was removed.
-    const int voff8 = ((rw + lr) * HID + cw + 4 * lg) * 2;
+    const int voff16 = ((rw + lr) * HID + cw + 8 * lg) * 2;
     const float sc = a.dh1_scale;
     uint32_t hv[NF][2];
     floatx4_t cs[NF];
 #pragma unroll
     for (int n = 0; n < NF; ++n) cs[n] = zero4();
+    // mask bytes of a row block's two fragment pairs (low byte: the nibble of the even
+    // fragment's 4 features, high byte: the odd one's), read one block ahead: the pad after
+    // the stores (below) would otherwise expose each block's LDS round trip
+    int mb[2][NF / 2];
+    auto masks = [&](int m) {
+#pragma unroll
+      for (int j = 0; j < NF / 2; ++j) mb[m & 1][j] = *reinterpret_cast<const uint16_t*>(M1b + (m * 16) * 64 + j * 8);
+    };
+    masks(0);
 #pragma unroll
     for (int m = 0; m < MF; ++m) {
+      if (m + 1 < MF) masks(m + 1);
 #pragma unroll
       for (int n = 0; n < NF; ++n) {
-        const int b = M1b[(m * 16) * 64 + n * 4];
+        const int b = mb[m & 1][n >> 1];
         floatx4_t v;
 #pragma unroll
         for (int r = 0; r < 4; ++r)  // bit r sign-extended to an all-ones / zero mask
-          v[r] = __int_as_float(__float_as_int(acc[m][n][r]) & __builtin_amdgcn_sbfe(b, r, 1));
+          v[r] = __int_as_float(__float_as_int(acc[m][n][r]) & __builtin_amdgcn_sbfe(b, (n & 1) * 8 + r, 1));
         cs[n] += v;
         const floatx4_t vs = v * sc;
         hv[n][0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(vs[0], vs[1]));
         hv[n][1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(vs[2], vs[3]));
       }
 #pragma unroll
-      for (int n = 0; n < NF; ++n) {
-        typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-        const u32x2_t h = {hv[n][0], hv[n][1]};
-        __builtin_amdgcn_raw_buffer_store_b64(h, dst, voff8, (m * 16 * HID + n * 16) * 2, OUT_AUX_NARROW);
+      for (int j = 0; j < NF / 2; ++j) {
+        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+        const u32x4_t h = {hv[2 * j][0], hv[2 * j][1], hv[2 * j + 1][0], hv[2 * j + 1][1]};
+        __builtin_amdgcn_raw_buffer_store_b128(h, dst, voff16, (m * 16 * HID + j * 32) * 2, OUT_AUX_NARROW);
       }
+      // A store of more than 64 bits still reads its data registers after issue.  hipcc's
+      // hazard recognizer pads a VALU write of them with a wait state, but not for a buffer
+      // store whose soffset is an SGPR -- and there it scheduled the next block's v_and into
+      // dword 0 of the data right behind the store.  With every CU in this phase the store
+      // then wrote that fp32 value: NaN / garbage in 16 dH1 columns at batch 65,536, exact
+      // results at 256 (profiles/r07_rows_epi).  Four wait states, and nothing scheduled across.
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_nop 3" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
     }
     // Transpose-reduce of the 16 column partials over the 16 rows of a DPP row: each
     // stage pairs lane i with i^15, i^7, i^2, i^1 (row_mirror, row_half_mirror, quad
     // perms), keeps the half of the values chosen by the lane bit the partners differ
     // in and adds the partner's other half.  Value index n*4 + r; lane lr ends with index
-    // lr0*8 + lr1*4 + lr2*2 + lr3 (lrK = bit K of lr).
+    // lr0*8 + lr1*4 + lr2*2 + lr3 (lrK = bit K of lr), i.e. feature 32 (n/2) + 8 lg + 4 (n%2) + r.
     static_assert(NF == 4, "16 partials per lane");
     float red[16];
 #pragma unroll
@@ -1011,7 +1053,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     stage(std::integral_constant<int, 0xB1>{}, lr & 1, 1);
     {
       const int n = 2 * (lr & 1) + ((lr >> 1) & 1), r = 2 * ((lr >> 2) & 1) + ((lr >> 3) & 1);
-      st_out(&a.w3p[(long)blockIdx.x * W3P_LD + W3P_DB1 + cw + n * 16 + 4 * lg + r], red[0]);
+      st_out(&a.w3p[(long)blockIdx.x * W3P_LD + W3P_DB1 + cw + (n >> 1) * 32 + 8 * lg + (n & 1) * 4 + r], red[0]);
     }
     stamp(15);
   } else {

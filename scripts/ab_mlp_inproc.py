@@ -6,8 +6,8 @@ measured.  Here one trainer on one batch re-captures its step graph for each arm
 arms alternate over R rounds of K timed steps; medians and per-round ratios are printed.
 
 Arms: rows-kernel tile heights ("--bm 64,128") or weight-gradient split-K slice counts
-("--slices 28,24", one trainer per arm).  Kernel libraries cannot be loaded side by side in one
-process: use scripts/ab_env.sh for those.
+("--slices 28,24", one trainer per arm).  Two builds of the kernel library: scripts/ab_mlp_libs.py
+(in one process) or scripts/ab_env.sh (one process per arm).
 Usage: python scripts/ab_mlp_inproc.py [--bm 64,128 | --slices 28,24] [--rounds 8] [--steps 50]
 """
 import argparse
