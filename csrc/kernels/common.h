@@ -102,18 +102,6 @@ __device__ __forceinline__ short8_t u8x8_to_bf16(uint2 v, float a, float b) {
   return r;
 }
 
-// Two waves per SIMD in one workgroup: the second-dispatched half loses issue arbitration to
-// the older half at every segment (priority, then age: MI355X_MICROARCH.md, two waves per
-// SIMD).  SL_WAVE_PRIO: that half raises its priority once, before the main loop (measured
-// neutral on the 8-wave conv and MLP weight-gradient kernels: profiles/r05_ce; off).
-#ifndef SL_WAVE_PRIO
-#define SL_WAVE_PRIO 0
-#endif
-__device__ __forceinline__ void younger_half_prio() {
-  if (SL_WAVE_PRIO && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= (int)(blockDim.x >> 7))
-    __builtin_amdgcn_s_setprio(1);
-}
-
 // XCD-aware bijective remap of a 1-D grid (cdna_hip_programming.md §5 T1):
 // consecutive logical tiles land on the same XCD so they share its L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -127,13 +115,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // those words (MI355X_MICROARCH.md "Global float atomics", contention row), so
 // each workgroup adds into replica (blockIdx % SL_REP) of a [SL_REP][n] array
 // and a separate launch, rsum_fold_kernel (conv.hip, sl_rsum_fold), folds the replicas
-// into out[n] once the producers are done (or, with SL_RSUM_ARRIVE=1, the producer
-// launch's last-arriving workgroup: rsum_arrive below).  The fold used to be done
-// by the last workgroup of the producer itself (agent-release fence + ticket per
-// workgroup): with ~1000-8000 workgroups per launch the per-workgroup release
-// (an L2 writeback on a multi-XCD part) and the single-address ticket cost
-// ~1 ms per ResNet-18 step (profiles/r02_rsum); the kernel boundary orders the
-// replica atomics for free.
+// into out[n] once the producers are done: the kernel boundary orders the replica
+// atomics for free.  The two in-kernel alternatives measured slower and were removed.
+// Folding in the producer launch's last-arriving workgroup (one ticket per workgroup)
+// makes every producer grow by about what its fold launch cost: ResNet-18 -1.3 %
+// (profiles/r05_arrive; with a release fence per workgroup ~1 ms per step,
+// profiles/r02_rsum).  Folding in each consumer's prologue costs every consumer
+// workgroup a 16 KB fold, more than the launch it removes: -1.6 % (profiles/r05_cons,
+// r06_cons).
 // Buffer layout (rsum_floats(n) floats, replicas zeroed before the producers):
 //   [SL_REP][n] replicas | [n] result | 4 pad
 // ---------------------------------------------------------------------------
@@ -171,23 +160,8 @@ __host__ __device__ __forceinline__ double fix_value(const unsigned long long* p
   return (double)(long long)p[0] * (1.0 / SL_FIX_HI) + (double)(long long)p[1] * (1.0 / SL_FIX_LO);
 }
 
-// Consumer-side fold (SL_RSUM_CONSUMER=1; default off: measured 1.6 % slower, profiles/r05_cons --
-// every consumer workgroup's 16 KB fold prologue costs more than the fold launch it removes):
-// the kernels that read a folded row
-// (BN apply, BN-backward apply, the direct 3x3 conv's BN-on-load) sum the replicas into LDS in
-// their prologue, and their workgroup 0 also writes the result row for later readers, so the
-// producer needs no fold launch when the host defers it (sl_rsum_set_defer; the ResNet engine
-// does so for its step).  For that, n values x the replicas in use stay within 16 KB:
-// rsum_reps(n) = min(SL_REP, 4096 / n) (64 channels: 32, 128: 16, 256: 8, 512: 4).
-#ifndef SL_RSUM_CONSUMER
-#define SL_RSUM_CONSUMER 0
-#endif
-constexpr int SL_RSUM_LDS = 1024;  // largest n folded in a consumer (C <= 512)
-__host__ __device__ constexpr int rsum_reps(int n) {
-  return !SL_RSUM_CONSUMER ? SL_REP : (4096 / n >= SL_REP ? SL_REP : (4096 / n < 1 ? 1 : 4096 / n));
-}
 __device__ __forceinline__ float* rsum_replica(float* buf, int n) {
-  return SL_DETERMINISTIC ? buf : buf + (long)(blockIdx.x % rsum_reps(n)) * n;
+  return SL_DETERMINISTIC ? buf : buf + (long)(blockIdx.x % SL_REP) * n;
 }
 __device__ __forceinline__ float* rsum_result(float* buf, int n) { return buf + (long)SL_REP * n; }
 // add v to entry i of a replica returned by rsum_replica
@@ -196,157 +170,6 @@ __device__ __forceinline__ void rsum_add(float* rep, long i, float v) {
   fix_add(reinterpret_cast<unsigned long long*>(rep) + 2 * i, v);
 #else
   atomicAdd(rep + i, v);
-#endif
-}
-
-// ---------------------------------------------------------------------------
-// Fold by the last-arriving workgroup (SL_RSUM_ARRIVE=1; default off): the producer's own
-// launch folds the replicas into the result row, so no rsum_fold launch follows it.  Measured
-// (profiles/r05_arrive): the 37 fold launches per ResNet-18 step go, but every producer grows
-// by about what its fold launch cost (+2.5-4.6 us: each workgroup now drains its epilogue
-// stores and waits for a returning ticket before it exits, and the last one reads the replicas
-// after that), and the step is 1.3 % slower; the separate launch stays the default.  Each
-// workgroup, after all of its replica atomics (every wave drains them: `s_waitcnt vmcnt(0)`,
-// then a workgroup barrier), takes a ticket with ONE agent-scope atomic add; the workgroup
-// whose add returns gridDim - 1 is the launch's last.  A producer may span several launches
-// adding into the same buffer (the four parity-class launches of a stride-2 data gradient):
-// the last arrival of each launch adds to a launch counter and the one completing `launches`
-// folds.  The replica atomics are performed past the CUs' caches and the folding workgroup
-// reads them with `sc1` loads after its own ticket returned (MI355X_MICROARCH.md, hand-off
-// table, first row); the result row goes out with plain stores and reaches its consumers
-// through the kernel boundary.  Both ticket words live in the buffer's pad (rsum_floats) and
-// are re-armed to 0 by the workgroup that completes them.
-// ---------------------------------------------------------------------------
-#ifndef SL_RSUM_ARRIVE
-#define SL_RSUM_ARRIVE 0
-#endif
-struct RsumFold {
-  float* buf;     // rsum buffer of n values (null: nothing to fold)
-  float* buf2;    // a second buffer folded by the same arrivals (nullable)
-  int n;
-  int launches;   // launches whose workgroups all add into buf (>= 1)
-};
-
-__device__ __forceinline__ void rsum_fold_row(float* buf, int n, int tid, int nthr) {
-  float* res = rsum_result(buf, n);
-  for (int i = tid; i < n; i += nthr) {
-#if SL_DETERMINISTIC
-    unsigned long long* p = reinterpret_cast<unsigned long long*>(buf) + 2 * i;
-    const long long hi = (long long)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const long long lo = (long long)__hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    res[i] = (float)((double)hi * (1.0 / SL_FIX_HI) + (double)lo * (1.0 / SL_FIX_LO));
-#else
-    float v[SL_REP];
-#pragma unroll
-    for (int r = 0; r < SL_REP; ++r) v[r] = __hip_atomic_load(buf + (long)r * n + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    float acc = 0.f;
-#pragma unroll
-    for (int r = 0; r < SL_REP; ++r) acc += v[r];  // the order rsum_fold_kernel sums in
-    res[i] = acc;
-#endif
-  }
-}
-
-// Consumer prologue: the folded n values of the rsum buffer whose result row is `res`, in
-// `lds` (SL_RSUM_LDS floats); workgroup 0 also stores them to the result row.  Every thread
-// calls it (it ends with a workgroup barrier); res null or on == 0 (the launcher ran outside a
-// deferral: res is a folded row, or any plain array of n values): returns res.
-// The replicas of an rsum buffer summed into lds[0..n) by the whole workgroup (publish: also
-// stored to the result row with plain stores).  Ends before the final barrier of its callers.
-__device__ __forceinline__ void rsum_consume_fold(const float* buf, int n, float* lds, bool publish) {
-#if SL_DETERMINISTIC
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const float acc = (float)fix_value(reinterpret_cast<const unsigned long long*>(buf) + 2 * i);
-    lds[i] = acc;
-    if (publish) const_cast<float*>(buf + (long)SL_REP * n)[i] = acc;
-  }
-#else
-  // every thread issues its (at most 16) replica loads at once: R * n <= 4096 values over the
-  // workgroup; n <= blockDim: tpe threads per value, each summing R / tpe replicas into LDS
-  const int R = rsum_reps(n), tid = threadIdx.x, nt = blockDim.x;
-  if (n <= nt) {
-    const int tpe = nt / n, e = tid % n, g = tid / n;
-    float v[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int r = g + k * tpe;
-      v[k] = (g < tpe && r < R) ? buf[(long)r * n + e] : 0.f;
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc += v[k];
-    if (g < tpe) lds[g * n + e] = acc;  // tpe * n <= nt <= SL_RSUM_LDS
-    __syncthreads();
-    if (tid < n) {
-      float t = lds[tid];
-      for (int q = 1; q < tpe; ++q) t += lds[q * n + tid];
-      lds[tid] = t;
-      if (publish) const_cast<float*>(buf + (long)SL_REP * n)[tid] = t;
-    }
-  } else {  // n = 512 / 1024: R <= 8, at most 4 values per thread
-    float v[4][8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int e = tid + j * nt;
-        v[j][r] = (e < n && r < R) ? buf[(long)r * n + e] : 0.f;
-      }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int e = tid + j * nt;
-      float t = 0.f;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) t += v[j][r];
-      if (e < n) {
-        lds[e] = t;
-        if (publish) const_cast<float*>(buf + (long)SL_REP * n)[e] = t;
-      }
-    }
-  }
-#endif
-}
-__device__ __forceinline__ const float* rsum_consume(const float* res, int n, float* lds, int on) {
-  if (!SL_RSUM_CONSUMER || !on || !res || n > SL_RSUM_LDS) return res;
-  rsum_consume_fold(res - (long)SL_REP * n, n, lds, blockIdx.x == 0);
-  __syncthreads();
-  return lds;
-}
-
-// host: the fold a producer launch carries (none when the separate fold launch is used)
-__host__ __device__ inline RsumFold rsum_fold_spec(float* buf, float* buf2, int n, int launches) {
-  return SL_RSUM_ARRIVE && buf ? RsumFold{buf, buf2, n, launches} : RsumFold{nullptr, nullptr, 0, 0};
-}
-
-// Every thread of the workgroup calls this once per launch, after all of the workgroup's
-// rsum_add calls into f.buf / f.buf2, in uniform control flow.
-__device__ __forceinline__ void rsum_arrive(const RsumFold& f) {
-#if !SL_RSUM_ARRIVE
-  (void)f;  // off: no ticket word, and no LDS word either (it would cost 4 B in every producer)
-#else
-  if (!f.buf) return;
-  __shared__ unsigned rsum_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's replica atomics are done
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned* t = reinterpret_cast<unsigned*>(f.buf + (long)(SL_REP + 1) * f.n);
-    unsigned last = 0;
-    if (__hip_atomic_fetch_add(t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-      __hip_atomic_store(t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = 1;
-      if (f.launches > 1) {
-        last = __hip_atomic_fetch_add(t + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-               (unsigned)f.launches - 1;
-        if (last) __hip_atomic_store(t + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    rsum_last = last;
-  }
-  __syncthreads();
-  if (rsum_last) {
-    rsum_fold_row(f.buf, f.n, threadIdx.x, blockDim.x);
-    if (f.buf2) rsum_fold_row(f.buf2, f.n, threadIdx.x, blockDim.x);
-  }
 #endif
 }
 

@@ -40,26 +40,9 @@ constexpr int TR = 8;                  // output rows per tile
 constexpr int TPIX = TR * IW;          // 256 output pixels per tile
 constexpr int HR = TR + 2, HCOL = IW + 2;  // halo 10 x 34 pixels
 constexpr int NTH = 256;
-#ifndef SL_HALO_WAVES
-#define SL_HALO_WAVES 8  // 8 measured +1% over 4 (two waves per SIMD); the deferred forward needs 8
-#endif
-constexpr int NWF = SL_HALO_WAVES;     // waves of the forward / dgrad kernel
-#ifndef SL_HALO_DEFER
-#define SL_HALO_DEFER 1  // plain forward: output stores deferred into the next tile's k-loop
-#endif
-#ifndef SL_HALO_EPI_PF
-// data gradient (no DEFER): issue the epilogue's residual / BN-input / mask loads at the top of
-// the tile's k-loop instead of after it, so their HBM latency hides under the MFMAs
-#define SL_HALO_EPI_PF 1
-#endif
-#ifndef SL_HALO_LDSBAR
-#define SL_HALO_LDSBAR 1  // LDS-only barriers inside the tile loop (see lds_bar)
-#endif
-#ifndef SL_HALO_KO
-// timing knockouts of conv3x3_kernel (results wrong; profiles/r03_haloko): 1 no epilogue global
-// traffic, 2 no halo loads after the first tile, 3 no MFMAs / fragment reads, 4 no epilogue
-#define SL_HALO_KO 0
-#endif
+// waves of the forward / dgrad kernel: two per SIMD (+1 % over 4, and the deferred forward's
+// store schedule needs 8)
+constexpr int NWF = 8;
 constexpr int NTF = 64 * NWF;
 constexpr int MF = TPIX / NWF / 16;    // m-fragments (16 output pixels) per wave
 constexpr int OUT_LD = 72;             // staging row stride (elements)
@@ -72,7 +55,7 @@ constexpr int STAGE_BYTES = TPIX * OUT_LD * 2;
 // have zero weights).  Pixel / weight-row strides in 16-B chunks are chosen
 // = 10 (mod 16) or brute-forced so ds_read_b128 lane groups stay (near)
 // conflict-free.
-// Branch-free loads (SL_HALO_BRFREE).  A load issued under a divergent (or path-dependent)
+// Branch-free loads (profiles/r05_brf).  A load issued under a divergent (or path-dependent)
 // condition, with the other path writing the same registers (the zero / 0xff default),
 // leaves the compiler's wait-count pass a pending write on that path: it then drains ALL
 // outstanding loads (s_waitcnt vmcnt(0) / (4)) before the next VALU write to those registers
@@ -80,18 +63,13 @@ constexpr int STAGE_BYTES = TPIX * OUT_LD * 2;
 // HBM latency on every tile.  Every lane therefore loads unconditionally from a valid
 // address (padding / surplus lanes: a clamped in-image pixel; absent operands: another
 // tensor of the same shape) and the value is masked where it is consumed.
-#ifndef SL_HALO_BRFREE
-#define SL_HALO_BRFREE 1
-#endif
 // keep v live here (the wait-count pass then settles its load on every path)
 template <typename T>
 __device__ __forceinline__ void halo_consume(const T& v) {
-  if constexpr (SL_HALO_BRFREE) {
-    if constexpr (sizeof(T) == 16) {
-      asm volatile("" ::"v"(__builtin_bit_cast(short8_t, v)));  // uint4 is a struct
-    } else {
-      asm volatile("" ::"v"(v));
-    }
+  if constexpr (sizeof(T) == 16) {
+    asm volatile("" ::"v"(__builtin_bit_cast(short8_t, v)));  // uint4 is a struct
+  } else {
+    asm volatile("" ::"v"(v));
   }
 }
 
@@ -125,8 +103,6 @@ struct HaloArgs {
   // coefficients and running statistics, as bn_apply_stats would have
   BnStats bin;
   float bin_count, bin_eps, bin_momentum;
-  RsumFold fold;        // stats or bn.sums, folded by the last workgroup (common.h)
-  int bin_consume;      // bin.stats is an unfolded rsum buffer's result row: fold it here (rsum_consume)
 };
 
 // DEFER (plain forward: no residual, no fused BN backward): the bf16 output tile is staged in
@@ -140,12 +116,11 @@ __device__ __forceinline__ int cs_swz(int p, int chunk) { return p * (HC * 2) + 
 // apply BN-on-load (a.bin).  Separate instances, so neither carries the other's registers.
 template <int CIN, bool DEFER, bool BNB>
 __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
-  younger_half_prio();
   using L = Lay<CIN>;
   constexpr int HL = (L::HALO_CHUNKS + NTF - 1) / NTF;  // halo chunks per thread
   static_assert(!DEFER || L::REGION + L::W_BYTES + DEFER_BYTES <= 160 * 1024, "deferred image must fit LDS");
   // the deferred stores cover a tile in 4 passes of NTF / 8 pixels (k-step pairs 1, 3, 5, 7)
-  static_assert(!DEFER || 4 * NTF / 8 == TPIX, "DEFER needs 8 waves (SL_HALO_WAVES=4 stored half the tile)");
+  static_assert(!DEFER || 4 * NTF / 8 == TPIX, "DEFER needs 8 waves");
   __shared__ __attribute__((aligned(16))) uint8_t smem[L::REGION + L::W_BYTES + (DEFER ? DEFER_BYTES : 0)];
   uint8_t* Hs = smem;
   uint8_t* Ws = smem + L::REGION;
@@ -156,15 +131,12 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
   const int tiles_per_img = a.H / TR;
   // The tile loop's barriers order LDS traffic only (halo / staging / Ds images): waiting for
   // lgkmcnt suffices.  __syncthreads() would also drain every outstanding global store
-  // (vmcnt(0)), stalling the data gradient on its own output tile's HBM writes once per tile.
+  // (vmcnt(0)), stalling the data gradient on its own output tile's HBM writes once per tile
+  // (profiles/r05_haloepi).
   auto lds_bar = [&]() __attribute__((always_inline)) {
-    if constexpr (SL_HALO_LDSBAR) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    } else {
-      __syncthreads();
-    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
   };
 
   // ---- weights -> LDS, once (flip applied here, so the k-loop is tap-agnostic) ----
@@ -181,12 +153,12 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
   const bool bni = CIN == 64 && !BNB && a.bin.stats != nullptr;
   float isc[8], ish[8];
   if (bni) {
-    // the input BN's replicas folded into the (still free) halo region (rsum_consume)
-    BnStats bs = a.bin;
-    bs.stats = rsum_consume(a.bin.stats, 2 * HC, reinterpret_cast<float*>(Hs), a.bin_consume);
-    bn_coef8(bs, HC, (tid & 7) * 8, a.bin_count, a.bin_eps, isc, ish);
-    if (blockIdx.x == 0) bn_publish(bs, HC, a.bin_count, a.bin_eps, a.bin_momentum);
-    __syncthreads();  // the fold's reads are done before the first halo lands in Hs
+    bn_coef8(a.bin, HC, (tid & 7) * 8, a.bin_count, a.bin_eps, isc, ish);
+    if (blockIdx.x == 0) bn_publish(a.bin, HC, a.bin_count, a.bin_eps, a.bin_momentum);
+    // left from the removed consumer-side fold (it staged the sums in Hs): nothing here needs
+    // this barrier now; it stays so that removing the fold left the measured code as it was
+    // (profiles/r08_knobs) and goes with the next change that re-measures this kernel
+    __syncthreads();
   }
 
   // ---- halo tile: global -> registers (prefetch) -> LDS ----
@@ -204,14 +176,9 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
       const int hr = pix / HCOL, hc = pix - hr * HCOL;
       const int ih = r0 - 1 + hr, iw = hc - 1;
       const bool ok = q < L::HALO_CHUNKS && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)IW;
-      if constexpr (SL_HALO_BRFREE) {
-        // out-of-range buffer offset: the load returns zeros without a memory access
-        const int off = ok ? ((ih * IW + iw) * CIN + c * 8) * 2 : (int)0x7ffffff0;
-        hv[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-      } else {
-        hv[i] = ok ? *reinterpret_cast<const uint4*>(a.src + (((long)img * a.H + ih) * IW + iw) * CIN + c * 8)
-                   : make_uint4(0, 0, 0, 0);
-      }
+      // out-of-range buffer offset: the load returns zeros without a memory access
+      const int off = ok ? ((ih * IW + iw) * CIN + c * 8) * 2 : (int)0x7ffffff0;
+      hv[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
       hok |= (unsigned)ok << i;
     }
   };
@@ -268,7 +235,8 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
   halo_store();
   __syncthreads();
   // residual / BN operands of this thread's epilogue chunks (tile pixel p = (tid + k NTF) / 8,
-  // channels (tid & 7) * 8 ..): SL_HALO_EPI_PF issues them before the k-loop
+  // channels (tid & 7) * 8 ..), issued at the top of the tile's k-loop so their HBM latency
+  // hides under the MFMAs (profiles/r05_haloepi)
   constexpr int EIT = TPIX * 8 / NTF;
   const int ec = (tid & 7) * 8;
   short8_t ea[EIT];
@@ -278,7 +246,6 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
 #pragma unroll
     for (int k = 0; k < EIT; ++k) {
       const long off = (pix0 + ((tid + k * NTF) >> 3)) * a.ldy + ec;
-      if (SL_HALO_KO == 1) continue;
       // uniform conditions: these loads stay conditional; halo_consume settles them per tile
       if (a.add) ea[k] = ld8(a.add + off);
       if (bnb) bnb_load<false>(a.bn, off, ebn[k]);
@@ -286,10 +253,10 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
   };
   for (; t < a.tiles; t += gridDim.x) {
     const int next = t + gridDim.x;
-    if (next < a.tiles && SL_HALO_KO != 2) halo_load(next);  // lands under this tile's MFMAs
-    if constexpr (!DEFER && SL_HALO_EPI_PF) epi_loads(t);    // ... and so do these
+    if (next < a.tiles) halo_load(next);     // lands under this tile's MFMAs
+    if constexpr (!DEFER) epi_loads(t);      // ... and so do these
     // unconditional loads would otherwise sink below the k-loop, next to their first use
-    if constexpr (SL_HALO_BRFREE) asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");
 
     floatx4_t acc[MF][4];
 #pragma unroll
@@ -335,21 +302,14 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
       }
       if (s + 1 < L::NKS) frag_reads(s + 1, a1, b1);
       __builtin_amdgcn_sched_barrier(0);
-      if (SL_HALO_KO != 3) mfmas(a0, b0);
+      mfmas(a0, b0);
       __builtin_amdgcn_sched_barrier(0);
       if (s + 2 < L::NKS) frag_reads(s + 2, a0, b0);
       __builtin_amdgcn_sched_barrier(0);
-      if (s + 1 < L::NKS && SL_HALO_KO != 3) mfmas(a1, b1);
+      if (s + 1 < L::NKS) mfmas(a1, b1);
       __builtin_amdgcn_sched_barrier(0);
     }
     lds_bar();  // every wave is done with this halo
-    if (SL_HALO_KO == 4) {
-      if (next < a.tiles) {
-        halo_store();
-        __syncthreads();
-      }
-      continue;
-    }
 
     // ---- epilogue: statistics in registers, bf16 tile staged through LDS ----
     if (a.stats) {
@@ -392,10 +352,8 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           Cs[(wave * (TPIX / NWF) + i * 16 + 4 * lg + r) * OUT_LD + j * 16 + lr] = f2bf(acc[i][j][r]);
-    // without SL_HALO_EPI_PF the operands are issued here, in flight under the staging barrier
     const long pix0 = (long)t * TPIX;  // tiles are whole 8-row bands: pixel index = tile * 256
     const int c = ec;
-    if constexpr (!SL_HALO_EPI_PF) epi_loads(t);
     lds_bar();
 #pragma unroll
     for (int k = 0; k < EIT; ++k) {
@@ -405,10 +363,6 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
       if (a.add) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (short)f2bf(bf2f((uint16_t)v[e]) + bf2f((uint16_t)ea[k][e]));
-      }
-      if (SL_HALO_KO == 1) {
-        if (v[0] == 12345) a.y[m * a.ldy + c] = 0;  // keeps the staging read alive
-        continue;
       }
       if (bnb) bnb_chunk<false>(a.bn, ebn[k], v, msc, msh, bacc);
       *reinterpret_cast<short8_t*>(a.y + m * a.ldy + c) = v;
@@ -463,10 +417,8 @@ __global__ __launch_bounds__(NTF, 1) void conv3x3_kernel(HaloArgs a) {
     __syncthreads();  // the last tile's staging reads are done (no halo follows)
     bnb_fold<NTF, HC / 8>(a.bn, bacc, reinterpret_cast<float*>(smem), 0, HC);
   }
-  rsum_arrive(a.fold);
 }
 
-extern "C" int sl_rsum_defer();  // conv.hip
 static int g_halo_enabled = -1;  // -1: from SL_CONV_HALO (default on)
 static int g_num_cus = 0;
 
@@ -513,18 +465,16 @@ static int conv3x3_launch(const uint16_t* src, const uint16_t* w, int cin, int f
   if (bn) a.bn = *bn;
   a.bin = BnStats{};
   a.bin_count = bin_count; a.bin_eps = bin_eps; a.bin_momentum = bin_momentum;
-  a.bin_consume = sl_rsum_defer();
-  a.fold = stats ? rsum_fold_spec(stats, nullptr, 2 * HC, 1)
-                 : rsum_fold_spec(bn ? bn->sums : nullptr, nullptr, 2 * HC, 1);
   if (bin) {
     if (cin != 64 || flip || !bin->stats || !bin->gamma || !bin->beta || !bin->coef || bin_count <= 0.f) return -4;
     a.bin = *bin;
   }
   const int grid = a.tiles < g_num_cus ? a.tiles : g_num_cus;  // persistent: one workgroup per CU (130 KB LDS)
-  // the plain forward defers its output stores into the next tile's k-loop; deferring the data
+  // the plain forward defers its output stores into the next tile's k-loop (profiles/r03_haloko);
+  // deferring the data
   // gradient's epilogue (residual add + fused BN backward) too measured 152.8 vs 138 us per call
   // and the stem's needs its 3-step k-loop re-planned (profiles/r04_haloepi)
-  const bool defer = SL_HALO_DEFER && cin == 64 && !flip && !add && !bn;
+  const bool defer = cin == 64 && !flip && !add && !bn;
   if (cin == 8) {
     if (bn) return -2;
     hipLaunchKernelGGL((conv3x3_kernel<8, false, false>), dim3(grid), dim3(NTF), 0, stream, a);
@@ -560,7 +510,7 @@ int sl_conv3x3_bnin_fwd(const uint16_t* x, const uint16_t* w, int N, int H, uint
                         float* run_var, float count, float eps, float momentum, hipStream_t stream) {
   const BnStats bin{bstats, gamma, beta, coef, run_mean, run_var};
   const int rc = conv3x3_launch(x, w, 64, 0, N, H, y, ldy, nullptr, stats, nullptr, &bin, count, eps, momentum, stream);
-  if (rc || !stats || SL_RSUM_ARRIVE || sl_rsum_defer()) return rc;
+  if (rc || !stats) return rc;
   return sl_rsum_fold(stats, 2 * HC, stream);  // as sl_conv_fwd does after its epilogue sums
 }
 
@@ -578,27 +528,24 @@ int sl_conv3x3_bnin_fwd(const uint16_t* x, const uint16_t* w, int N, int H, uint
 // channels ci 16 (w & 3) .. +15 of taps 0-4 (w < 4) or 5-8, i.e. 20 or 16
 // accumulator tiles; the workgroup's partial dW is added with fp32 atomics
 // once at the end (one adder per CU per address).
-// LDS images (SL_HWG_SWZ = 1): unpadded 128-B pixels, 16-B chunk c of pixel x at
+// LDS images: unpadded 128-B pixels, 16-B chunk c of pixel x at
 // position c ^ (g(x) << 1), g(x) = bit 1 | bit 3 << 1 of x.  A tr-read lane half takes
 // pixels {b .. b+3, b+8 .. b+11} x 32 B; g spreads each parity class of those pixels over
 // the four chunk pairs, so every half covers the 64 banks once (brute-forced over all
 // fragments; the stores stay one contiguous 128-B pixel per 8 lanes).  The per-lane
 // address then depends on the fragment's first pixel mod 16: one base VGPR per residue.
-// SL_HWG_SWZ = 0: the round-3 144-B pixel stride, where every tr-read half is 2-way
-// (44 % of the kernel's LDS cycles were conflicts, profiles/r05_pmc_cnn).  The implicit-
-// GEMM path re-gathered X 9 times through LDS-DMA instead.
+// (A padded 144-B pixel stride leaves every tr-read half 2-way: 44 % of the kernel's LDS
+// cycles were conflicts, profiles/r05_pmc_cnn, r05_hwg.)  The implicit-GEMM path re-gathered
+// X 9 times through LDS-DMA instead.
 // ---------------------------------------------------------------------------
-#ifndef SL_HWG_SWZ
-#define SL_HWG_SWZ 1
-#endif
 namespace {
 constexpr int WNT = 512;                    // threads
-constexpr int WPS = SL_HWG_SWZ ? 128 : 144; // pixel stride (bytes) of both LDS images
-constexpr int WX_BYTES = HR * HCOL * WPS;   // 43,520 (48,960 at 144)
-constexpr int WY_BYTES = TPIX * WPS;        // 32,768 (36,864)
+constexpr int WPS = 128;                    // pixel stride (bytes) of both LDS images
+constexpr int WX_BYTES = HR * HCOL * WPS;   // 43,520
+constexpr int WY_BYTES = TPIX * WPS;        // 32,768
 // byte offset of 16-B chunk c inside pixel x's row
 __host__ __device__ constexpr int wg_chunk_off(int x, int c) {
-  return SL_HWG_SWZ ? ((c ^ ((((x >> 1) & 1) | (((x >> 3) & 1) << 1)) << 1)) << 4) : c << 4;
+  return (c ^ ((((x >> 1) & 1) | (((x >> 3) & 1) << 1)) << 1)) << 4;
 }
 constexpr int WX_CHUNKS = HR * HCOL * 8, WY_CHUNKS = TPIX * 8;
 constexpr int WLOADS = (WX_CHUNKS + WY_CHUNKS + WNT - 1) / WNT;  // 10 x 16 B per thread
@@ -621,15 +568,6 @@ __device__ __forceinline__ short4_t tr16_at(uint32_t a) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(a), "i"(OFF));
   return r;
 }
-template <int OFF0, int OFF1>
-__device__ __forceinline__ short8_t tr16_frag(uint32_t a) {
-  const short4_t lo = tr16_at<OFF0>(a), hi = tr16_at<OFF1>(a);
-  short8_t r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
-#if SL_HWG_SWZ
 // Per-lane bases: xb[r] / yb[r] address the lane's 8 B of a fragment whose first pixel is
 // = r (mod 16), minus that pixel's 16-aligned part (added as the instruction offset).
 // Y chunk pair I enters by XOR on address bits 5-6 (yb[r] holds pair 0; Ys is 128-B aligned).
@@ -655,18 +593,6 @@ __device__ __forceinline__ short8_t yfrag(const WgBases& yb) {
   r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
   return r;
 }
-#else
-using WgBases = uint32_t;
-// X fragment for tap T at output row S: halo pixel (S + T / 3, col + T % 3)
-template <int S, int T>
-__device__ __forceinline__ short8_t xfrag(uint32_t xb) {
-  return tr16_frag<((S + T / 3) * HCOL + T % 3) * WPS, ((S + T / 3) * HCOL + T % 3 + 4) * WPS>(xb);
-}
-template <int S, int I>
-__device__ __forceinline__ short8_t yfrag(uint32_t yb) {
-  return tr16_frag<(S * 32) * WPS + 32 * I, (S * 32 + 4) * WPS + 32 * I>(yb);
-}
-#endif
 
 template <int T0, int NTAP>
 __device__ __forceinline__ void wgrad_tile_mfmas(const WgBases& xb, const WgBases& yb, floatx4_t (&acc)[4][5]) {
@@ -748,7 +674,6 @@ __global__ __launch_bounds__(256) void halo_wgrad_reduce_kernel(const float4* __
 }
 
 __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs a) {
-  younger_half_prio();
   __shared__ __attribute__((aligned(128))) uint8_t smem[WX_BYTES + WY_BYTES];
   uint8_t* Xs = smem;
   uint8_t* Ys = smem + WX_BYTES;
@@ -763,7 +688,7 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs
   if (bni) bn_coef8(a.bin, HC, (tid & 7) * 8, a.bin_count, a.bin_eps, isc, ish);
 
   uint4 pv[WLOADS];
-  uint4 pvy[WLOADS];  // SL_HALO_BRFREE: Y half of a range that holds X and Y chunks
+  uint4 pvy[WLOADS];  // Y half of a range that holds X and Y chunks
   unsigned xok = 0;  // bit i: chunk i is an X chunk inside the image
   auto tile_load = [&](int tile) __attribute__((always_inline)) {
     const int img = tile / tiles_per_img, r0 = (tile - img * tiles_per_img) * TR;
@@ -775,58 +700,39 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs
 #pragma unroll
     for (int i = 0; i < WLOADS; ++i) {
       const int c = tid + i * WNT;
-      if constexpr (SL_HALO_BRFREE) {
-        // X and Y chunks through two buffer resources; a lane's offset is out of range in the
-        // one it does not use (and in both past the last Y chunk), which loads zeros for free.
-        // Workgroup-uniform i ranges touch one resource only.
-        constexpr int OOB = 0x7ffffff0;
-        const int i0 = i * WNT;
-        int xoff = OOB, yoff = OOB;
-        if (c < WX_CHUNKS) {
-          const int pix = c >> 3, ch = c & 7;
-          const int hr = pix / HCOL, hc = pix - hr * HCOL;
-          const int ih = r0 - 1 + hr, iw = hc - 1;
-          if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)IW) {
-            xoff = ((ih * IW + iw) * HC + ch * 8) * 2;
-            xok |= 1u << i;
-          }
-        } else if (c < WX_CHUNKS + WY_CHUNKS) {
-          const int cc = c - WX_CHUNKS;
-          yoff = ((cc >> 3) * a.ldy + (cc & 7) * 8) * 2;
-        }
-        if (i0 < WX_CHUNKS) pv[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff, 0, 0));
-        if (i0 + WNT > WX_CHUNKS && i0 < WX_CHUNKS + WY_CHUNKS) {
-          // a range holding both kinds keeps its Y half apart until tile_store (an OR here
-          // would wait for both loads before the MFMAs)
-          uint4& dst = i0 < WX_CHUNKS ? pvy[i] : pv[i];
-          dst = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(yrs, yoff, 0, 0));
-        }
-        continue;
-      }
-      uint4 v = make_uint4(0, 0, 0, 0);
+      // X and Y chunks through two buffer resources; a lane's offset is out of range in the
+      // one it does not use (and in both past the last Y chunk), which loads zeros for free.
+      // Workgroup-uniform i ranges touch one resource only.
+      constexpr int OOB = 0x7ffffff0;
+      const int i0 = i * WNT;
+      int xoff = OOB, yoff = OOB;
       if (c < WX_CHUNKS) {
         const int pix = c >> 3, ch = c & 7;
         const int hr = pix / HCOL, hc = pix - hr * HCOL;
         const int ih = r0 - 1 + hr, iw = hc - 1;
         if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)IW) {
-          v = *reinterpret_cast<const uint4*>(a.x + (((long)img * a.H + ih) * IW + iw) * HC + ch * 8);
+          xoff = ((ih * IW + iw) * HC + ch * 8) * 2;
           xok |= 1u << i;
         }
       } else if (c < WX_CHUNKS + WY_CHUNKS) {
-        const int cc = c - WX_CHUNKS, pix = cc >> 3, ch = cc & 7;
-        v = *reinterpret_cast<const uint4*>(a.dy + ((long)tile * TPIX + pix) * a.ldy + ch * 8);
+        const int cc = c - WX_CHUNKS;
+        yoff = ((cc >> 3) * a.ldy + (cc & 7) * 8) * 2;
       }
-      pv[i] = v;
+      if (i0 < WX_CHUNKS) pv[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff, 0, 0));
+      if (i0 + WNT > WX_CHUNKS && i0 < WX_CHUNKS + WY_CHUNKS) {
+        // a range holding both kinds keeps its Y half apart until tile_store (an OR here
+        // would wait for both loads before the MFMAs)
+        uint4& dst = i0 < WX_CHUNKS ? pvy[i] : pv[i];
+        dst = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(yrs, yoff, 0, 0));
+      }
     }
   };
   auto tile_store = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < WLOADS; ++i) {
       const int c = tid + i * WNT;
-      if constexpr (SL_HALO_BRFREE) {
-        if (i * WNT < WX_CHUNKS && (i + 1) * WNT > WX_CHUNKS) {  // mixed range: one of the two is zeros
-          pv[i].x |= pvy[i].x; pv[i].y |= pvy[i].y; pv[i].z |= pvy[i].z; pv[i].w |= pvy[i].w;
-        }
+      if (i * WNT < WX_CHUNKS && (i + 1) * WNT > WX_CHUNKS) {  // mixed range: one of the two is zeros
+        pv[i].x |= pvy[i].x; pv[i].y |= pvy[i].y; pv[i].z |= pvy[i].z; pv[i].w |= pvy[i].w;
       }
       if (c < WX_CHUNKS) {
         uint4 v = pv[i];
@@ -840,7 +746,6 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs
   };
 
   // tr16 lane addressing: rows = pixels 8 lg + q (+4 for the second read), columns = 4 p .. 4 p + 3
-#if SL_HWG_SWZ
   static_assert(WX_BYTES % 128 == 0, "Ys must stay 128-B aligned for the chunk-pair XOR");
   const uint32_t xs0 = (uint32_t)(uintptr_t)(SL_LDS const uint8_t*)Xs;
   const uint32_t ys0 = (uint32_t)(uintptr_t)(SL_LDS const uint8_t*)Ys;
@@ -851,10 +756,6 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs
     xb[r] = xs0 + (uint32_t)(x * WPS + wg_chunk_off(x, 2 * cb + (p >> 1)) + (p & 1) * 8);
     yb[r] = ys0 + (uint32_t)(x * WPS + wg_chunk_off(x, p >> 1) + (p & 1) * 8);
   }
-#else
-  const uint32_t xb = (uint32_t)(uintptr_t)(SL_LDS const uint8_t*)Xs + (uint32_t)((8 * lg + q) * WPS + (16 * cb + 4 * p) * 2);
-  const uint32_t yb = (uint32_t)(uintptr_t)(SL_LDS const uint8_t*)Ys + (uint32_t)((8 * lg + q) * WPS + 4 * p * 2);
-#endif
 
   floatx4_t acc[4][5];
 #pragma unroll
@@ -872,7 +773,7 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs
     for (; tile < a.tiles; tile += gridDim.x) {
       const int next = tile + gridDim.x;
       if (next < a.tiles) tile_load(next);
-      if constexpr (SL_HALO_BRFREE) asm volatile("" ::: "memory");  // keep the prefetch ahead of the MFMAs
+      asm volatile("" ::: "memory");  // keep the prefetch ahead of the MFMAs
       wgrad_tile_mfmas<T0, NTAP>(xb, yb, acc);
       __syncthreads();  // all waves done with this tile's images
       if (next < a.tiles) {
@@ -882,7 +783,7 @@ __global__ __launch_bounds__(WNT, 1) void conv3x3_wgrad_c64_kernel(WgradHaloArgs
 #pragma unroll
         for (int i = 0; i < WLOADS; ++i) {  // as halo_settle
           halo_consume(pv[i]);
-          if (SL_HALO_BRFREE && i * WNT < WX_CHUNKS && (i + 1) * WNT > WX_CHUNKS) halo_consume(pvy[i]);
+          if (i * WNT < WX_CHUNKS && (i + 1) * WNT > WX_CHUNKS) halo_consume(pvy[i]);
         }
       }
     }

@@ -42,24 +42,8 @@
 using namespace sl;
 
 namespace {
-// Cache policy of the stores that hand a kernel's outputs to the next launch: 16 = sc1
-// (write-through), 0 = default write-back (kept: write-through halves the launch gaps but
-// stretches the kernels by more, profiles/r05_sc1).  OUT_AUX: whole-line 16-B stores (H1 / dH2 rows,
-// weight-gradient slabs); OUT_AUX_NARROW: the partial-line ones (dH1's 16-B fragment rows, the
-// w3p partials' 4-B stores).
-#ifndef SL_STORE_AUX
-#define SL_STORE_AUX 0
-#endif
-#ifndef SL_STORE_AUX_NARROW
-#define SL_STORE_AUX_NARROW 0
-#endif
-constexpr int OUT_AUX = SL_STORE_AUX;
-constexpr int OUT_AUX_NARROW = SL_STORE_AUX_NARROW;
-__device__ __forceinline__ void st_out(float* p, float v) {
-  if constexpr (OUT_AUX_NARROW & 16) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-}
-
+// The stores that hand a kernel's outputs to the next launch use the default write-back policy:
+// write-through (sc1) halves the launch gaps but stretches the kernels by more (profiles/r05_sc1).
 constexpr int D_IN = 784;   // input features (28x28)
 constexpr int D_INP = 832;  // layer-1 K padded to 13 chunks of 64 (w1h row stride)
 constexpr int NCHUNK = D_INP / 64;
@@ -171,15 +155,9 @@ struct FragSrcPair {
 constexpr int ROW_STAMPS = 20;
 // Wave priority of the younger of the two workgroups that share a CU (dispatch order: the grid's
 // second half within each XCD; every one of the 256 CU pairs measured is one older + one younger).
-// 0: off (age decides: the older workgroup wins issue, finishes ~25k cycles earlier and the
-// younger runs its tail alone); 1 (default): the younger raises its priority after layer 1 and
-// the pair ends together (driver form +2.3 %, profiles/r05_prio); 2: after the softmax (neutral).
-#ifndef SL_ROWS_PRO_LATE
-#define SL_ROWS_PRO_LATE 1  // rows kernel (128-row tile): bias prologue after the stream's first loads
-#endif
-#ifndef SL_ROWS_PRIO
-#define SL_ROWS_PRIO 1
-#endif
+// Left to age, the older workgroup wins issue, finishes ~25k cycles earlier and the younger runs
+// its tail alone; the younger raises its priority after layer 1 and the pair ends together
+// (driver form +2.3 %, profiles/r05_prio; raising it after the softmax instead was neutral).
 
 struct MlpRowArgs {
   const uint8_t* x;
@@ -324,7 +302,7 @@ __device__ __forceinline__ void copy_part_buf(const uint16_t* src, int ld, __amd
     const short8_t v = *reinterpret_cast<const short8_t*>(src + rr * ld + c);
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), dst, (r * gld + c) * 2,
-                                           (it * PER + i) * RPP * gld * 2, OUT_AUX);
+                                           (it * PER + i) * RPP * gld * 2, 0);
   }
 }
 
@@ -374,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lg = lane >> 4;
   const int row0 = blockIdx.x * BM;
-  const bool young = (int)(blockIdx.x >> 3) >= (int)(gridDim.x >> 4);  // SL_ROWS_PRIO
+  const bool young = (int)(blockIdx.x >> 3) >= (int)(gridDim.x >> 4);  // the CU pair's younger workgroup
   const long srow0 = batch_base(a.cursor, a.n_batches, a.batch) + row0;
   const int wng = wave;
   const int cw = wng * 16 * NF;  // this wave's output columns
@@ -413,9 +391,9 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     if (BIG && tid < HID / 4) reinterpret_cast<float4*>(BS + HID)[tid] = b2v;
     BS[tid] = b1v + (a.xb - 1024.f * a.xa) * (float)((double)rs * (1.0 / R1_FIX));
   };
-  // SL_ROWS_PRO_LATE (128-row tile): issued after layer 1's first X chunks and weight-ring
-  // stages, so its memory round trip overlaps theirs instead of preceding them
-  if constexpr (!(BIG && SL_ROWS_PRO_LATE)) bias_prologue();
+  // 128-row tile: issued after layer 1's first X chunks and weight-ring stages, so its memory
+  // round trip overlaps theirs instead of preceding them (profiles/r05_prolate)
+  if constexpr (!BIG) bias_prologue();
   if (a.stamps && tid == 0) {  // placement: HW_ID (CU / SH / SE) and XCC_ID
     a.stamps[(long)blockIdx.x * ROW_STAMPS + 10] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
     a.stamps[(long)blockIdx.x * ROW_STAMPS + 11] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20);
@@ -667,7 +645,6 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
         for (int m = 0; m < 8; ++m) pk[m] = u8x2_f16_biased(w[m >> 1], m & 1);
       };
       // prologue: chunks 0, 1 converted, 2, 3 waiting in registers
-#if SL_ROWS_PRO_LATE
       // every prologue load first (X chunks 0-3, the weight ring, then the biases), then one
       // wait: the bias fold's round trip no longer precedes the stream's, nor chunk 0/1's the ring's
       uint4 x01[2][XP];
@@ -693,25 +670,6 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
           xcvt(x01[c][p], pk);
           xput(c, p, pk);
         }
-#else
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int p = 0; p < XP; ++p) {
-          uint32_t pk[8];
-          xcvt(xload(c, p), pk);
-          xput(c, p, pk);
-        }
-#pragma unroll
-      for (int c = 2; c < 4; ++c)
-#pragma unroll
-        for (int p = 0; p < XP; ++p) xq[c & 1][p] = xload(c, p);
-      short8_t r[RING][NF];
-#pragma unroll
-      for (int i = 0; i < RING; ++i)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) r[i][n] = f_w1(n, i, KS1);
-#endif
       bar();
       __builtin_amdgcn_sched_barrier(0);
       const int swz = (lr >> 1) & 7;
@@ -752,9 +710,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     }
   }
   stamp(1);
-  if constexpr (SL_ROWS_PRIO == 1) {
-    if (young) __builtin_amdgcn_s_setprio(1);
-  }
+  if (young) __builtin_amdgcn_s_setprio(1);
   if constexpr (ONE) bar();  // the X ring shares the image H1 goes to
   stamp(12);
   relu_out(BS, R1, true, a.xa);
@@ -870,9 +826,6 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     }
   }
   if (!TRAIN) return;
-  if constexpr (SL_ROWS_PRIO == 2) {
-    if (young) __builtin_amdgcn_s_setprio(1);
-  }
   bar();
   stamp(5);
 
@@ -903,8 +856,8 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
       const int c = 4 * lg + r;
       if (c < NC) {
 #pragma unroll
-        for (int n = 0; n < NF; ++n) st_out(&part[c * HID + cw + n * 16 + lr], d3[n][r]);
-        if (wng == 0 && lr == 0) st_out(&part[NC * HID + c], db3[r]);
+        for (int n = 0; n < NF; ++n) part[c * HID + cw + n * 16 + lr] = d3[n][r];
+        if (wng == 0 && lr == 0) part[NC * HID + c] = db3[r];
       }
     }
   }
@@ -949,7 +902,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     if (lg == 0) {
       float* part = a.w3p + (long)blockIdx.x * W3P_LD + off;
 #pragma unroll
-      for (int n = 0; n < NF; ++n) st_out(&part[cw + n * 16 + lr], cs[n][0]);
+      for (int n = 0; n < NF; ++n) part[cw + n * 16 + lr] = cs[n][0];
     }
   };
   col_sums(R0, W3P_DB2);
@@ -1015,7 +968,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
       for (int j = 0; j < NF / 2; ++j) {
         typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
         const u32x4_t h = {hv[2 * j][0], hv[2 * j][1], hv[2 * j + 1][0], hv[2 * j + 1][1]};
-        __builtin_amdgcn_raw_buffer_store_b128(h, dst, voff16, (m * 16 * HID + j * 32) * 2, OUT_AUX_NARROW);
+        __builtin_amdgcn_raw_buffer_store_b128(h, dst, voff16, (m * 16 * HID + j * 32) * 2, 0);
       }
       // A store of more than 64 bits still reads its data registers after issue.  hipcc's
       // hazard recognizer pads a VALU write of them with a wait state, but not for a buffer
@@ -1053,7 +1006,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     stage(std::integral_constant<int, 0xB1>{}, lr & 1, 1);
     {
       const int n = 2 * (lr & 1) + ((lr >> 1) & 1), r = 2 * ((lr >> 2) & 1) + ((lr >> 3) & 1);
-      st_out(&a.w3p[(long)blockIdx.x * W3P_LD + W3P_DB1 + cw + (n >> 1) * 32 + 8 * lg + (n & 1) * 4 + r], red[0]);
+      a.w3p[(long)blockIdx.x * W3P_LD + W3P_DB1 + cw + (n >> 1) * 32 + 8 * lg + (n & 1) * 4 + r] = red[0];
     }
     stamp(15);
   } else {
@@ -1241,11 +1194,8 @@ __device__ __forceinline__ void wg_vmcnt(int younger) {
 // remaining 31 dW2 tiles -- 2 of the 28 dW2 pairs straddle XCDs, no dW1 group does.  The
 // generic remap (consecutive logical tiles per XCD, 9 per slice) splits about 7 slices
 // (profiles/r06_place: 195 MB read for 164 MB of operands).  Other grids keep it.
-#ifndef SL_WG_PLACE
-#define SL_WG_PLACE 1
-#endif
 __device__ __forceinline__ void wg_place(int bid, int nwg, int total_tiles, int& s, int& t) {
-  if (SL_WG_PLACE && nwg == 252 && total_tiles == 9) {
+  if (nwg == 252 && total_tiles == 9) {
     const int x = bid & 7, idx = bid >> 3;
     if (x < 7 && idx < 28) {
       s = 4 * x + idx / 7;
@@ -1268,7 +1218,6 @@ constexpr int WG_NJ = 2;  // 16-column B fragments per wave
 constexpr int WG_NF = WG_MI + WG_NJ;       // fragments per wave per k-step
 
 __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
-  younger_half_prio();
   __shared__ __attribute__((aligned(16))) uint16_t smem[WG_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: branches on it stay uniform
@@ -1567,7 +1516,7 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
       if (n < P.n_real) {
         typedef uint32_t u32x4w __attribute__((ext_vector_type(4)));
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, acc[i][j]), out_rs, out_voff,
-                                               (i * WG_NJ + j) * 1024, OUT_AUX);
+                                               (i * WG_NJ + j) * 1024, 0);
       }
     }
 
@@ -1601,7 +1550,7 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int q = 4 * (c0 + col) + j;
-      if (q < W3P_N || q >= W3P_DB1) st_out(&srow[TL_SMALL + q], tv[j]);
+      if (q < W3P_N || q >= W3P_DB1) srow[TL_SMALL + q] = tv[j];
     }
   }
   if (A.stamps && tid == 0) {
@@ -1934,9 +1883,6 @@ __global__ __launch_bounds__(64) void mlp_w1_rowsum_kernel(const uint16_t* w1h, 
 // separate row-sum launch is gone), then 1,024-parameter chunks of b1 W2 b2 W3 b3.
 // Inline xGMI mode: each workgroup waits for the step's signals first (xg_block_wait).
 constexpr int UPD_NT = 256;
-#ifndef SL_UPD_HOIST
-#define SL_UPD_HOIST 1
-#endif
 constexpr int UPD_W1_ROW4 = D_IN / 4;  // 196 float4 per W1 row
 constexpr int UPD_REST_TASKS = (int)((P_N - P_B1 + 4 * UPD_NT - 1) / (4 * UPD_NT));
 constexpr int UPD_TASKS = HID + UPD_REST_TASKS;
@@ -1960,8 +1906,8 @@ __device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& 
   __shared__ unsigned s_step;
   const int tid = threadIdx.x;
   if (a.cursor && blockIdx.x == 0 && tid == 0) atomicAdd(a.cursor, 1);
-  // SL_UPD_HOIST: the first work item's weight / momentum loads go out before the peer wait
-  // (they do not depend on the peers), so their latency overlaps the wait
+  // The first work item's weight / momentum loads go out before the peer wait
+  // (they do not depend on the peers), so their latency overlaps the wait (profiles/r06_hoist)
   auto item = [&](int task, long& i4, long& ic, bool& live) __attribute__((always_inline)) {
     const bool w1 = task < HID;
     const long first = w1 ? (long)task * UPD_W1_ROW4 : P_B1 / 4 + (long)(task - HID) * UPD_NT;
@@ -1972,7 +1918,7 @@ __device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& 
   long i4 = 0, ic = 0;
   bool live = false;
   float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = w4, v4 = w4;
-  if (SL_UPD_HOIST && (int)blockIdx.x < UPD_TASKS) {
+  if ((int)blockIdx.x < UPD_TASKS) {
     item(blockIdx.x, i4, ic, live);
     w4 = reinterpret_cast<const float4*>(a.w)[ic];
     if (a.mom) m4 = reinterpret_cast<const float4*>(a.mom)[ic];
@@ -1983,13 +1929,13 @@ __device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& 
   if constexpr (XG) {
     s = xg_block_step(x, &s_step);
     // this rank's slot was written by the launch before this one: no peer wait needed for it
-    if (SL_UPD_HOIST && x.chunk4 == 0 && (int)blockIdx.x < UPD_TASKS)
+    if (x.chunk4 == 0 && (int)blockIdx.x < UPD_TASKS)
       own = xg_load(xg_rsrc(x, x.rank), xg_slot_off(x, s) + (unsigned)(ic * 16));
     if (x.inline_sync) xg_block_wait(x, x.chunk4 > 0 ? 1 : 0, s);  // two-shot: the owners' reduced slots
   }
   for (int task = blockIdx.x; task < UPD_TASKS; task += gridDim.x) {
     const bool w1 = task < HID;  // uniform per workgroup
-    if (!SL_UPD_HOIST || task != (int)blockIdx.x) {
+    if (task != (int)blockIdx.x) {
       item(task, i4, ic, live);
       w4 = reinterpret_cast<const float4*>(a.w)[ic];
       m4 = a.mom ? reinterpret_cast<const float4*>(a.mom)[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2001,7 +1947,7 @@ __device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& 
         g = xg_load_reduced_any(x, s, ic);
       } else {
         float4 v[XG_MAX_WORLD];
-        const bool own_ready = SL_UPD_HOIST && task == (int)blockIdx.x;
+        const bool own_ready = task == (int)blockIdx.x;
 #pragma unroll
         for (int q = 0; q < XG_MAX_WORLD; ++q)
           if (q < x.world)

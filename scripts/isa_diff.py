@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 device assembly of csrc/kernels/*.hip, kernel by kernel, between a git
+revision and the working tree, for the default and the -DSL_DETERMINISTIC=1 build.  Text only.
+
+  scripts/isa_diff.py [REV] [old=new ...] [--loose]
+
+Prints SAME / DIFF / GONE / NEW per kernel; exits 1 on any DIFF or NEW.  `old=new` maps a
+renamed (mangled) kernel.  --loose is the check for a kernel whose parameter list changed: the
+scalar kernarg loads, waits and scalar register numbers are dropped and, of the descriptor, only
+VGPR count, accum offset and private segment size must be equal and the LDS size no larger.
+"""
+import concurrent.futures as cf, glob, os, re, subprocess, sys, tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
+         "-Wno-unused-command-line-argument", "--cuda-device-only", "-S", "-o", "-"]
+NORM = [(r"__hip_cuid_\w+", "__hip_cuid"), (r"(\.LBB|\.Lfunc_end|BB)\d+", r"\1"), (r"\s*;.*", "")]
+KEEP = ("next_free_vgpr", "accum_offset", "private_segment_fixed_size")
+
+
+def kernels(src, det, loose):
+    """{name: (normalised text, LDS bytes)} of one source file: each function body plus its descriptor"""
+    cmd = ["hipcc", *FLAGS, "-I" + os.path.dirname(src), src] + (["-DSL_DETERMINISTIC=1"] if det else [])
+    asm = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True).stdout
+    out = {}
+    for m in re.finditer(r"^(\w+):\s*; @\1\n.*?^\.Lfunc_end\d+:", asm, re.S | re.M):
+        desc = re.search(r"^\s*\.amdhsa_kernel %s\n.*?\.end_amdhsa_kernel" % m.group(1), asm, re.S | re.M)
+        desc = desc.group(0) if desc else ""
+        body = m.group(0).replace(desc, "")  # the descriptor sits inside the function's span
+        lds = re.search(r"group_segment_fixed_size (\d+)", desc)
+        if loose:
+            body = "\n".join(l for l in body.splitlines() if not re.match(r"\s*s_(load|waitcnt)", l))
+            body = re.sub(r"\bs(\d+|\[\d+:\d+\])", "s", body)
+            desc = "\n".join(l.strip() for l in desc.splitlines() if any(k in l for k in KEEP))
+        text = body + "\n" + desc
+        for pat, rep in NORM:
+            text = re.sub(pat, rep, text)
+        out[m.group(1)] = ("\n".join(l.rstrip() for l in text.splitlines() if l.strip()), int(lds.group(1)) if lds else 0)
+    return out
+
+
+def main(argv):
+    loose = "--loose" in argv
+    argv = [a for a in argv if a != "--loose"]
+    rename = dict(a.split("=") for a in argv if "=" in a)
+    rev = ([a for a in argv if "=" not in a] or ["HEAD"])[0]
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp, cf.ThreadPoolExecutor(16) as pool:
+        subprocess.run("git archive %s csrc/kernels | tar -x -C %s" % (rev, tmp), shell=True, check=True, cwd=ROOT)
+        for det in (False, True):
+            side = []
+            for root in (tmp, ROOT):
+                srcs = sorted(glob.glob(os.path.join(root, "csrc", "kernels", "*.hip")))
+                side.append((srcs, [pool.submit(kernels, s, det, loose) for s in srcs]))
+            old, new = ({k: (os.path.basename(s), v) for s, f in zip(*sd) for k, v in f.result().items()} for sd in side)
+            old = {rename.get(k, k): (f, v) for k, (f, v) in old.items()}
+            for k in sorted(set(old) | set(new)):
+                f, a = old.get(k, (None, None))
+                f, b = new.get(k, (f, None))
+                was = next((o for o, n in rename.items() if n == k), k)  # the name the old text carries
+                same = a and b and a[0] == b[0].replace(k, was) and b[1] <= a[1]
+                verdict = "GONE" if b is None else "NEW" if a is None else "SAME" if same else "DIFF"
+                bad += verdict in ("DIFF", "NEW")
+                print("%-4s %-7s %-18s %s" % (verdict, "det" if det else "default", f, k))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
