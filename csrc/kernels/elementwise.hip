@@ -1,4 +1,4 @@
-// Memory-bound helper kernels: gossip delta-apply (K7) and flat fused SGD (K5).
+// Memory-bound helper kernels: gossip delta-apply (K7), flat fused SGD (K5) and gradient clipping.
 #include "common.h"
 
 using namespace sl;
@@ -167,6 +167,84 @@ __global__ __launch_bounds__(256) void opt_flat_kernel(float* __restrict__ w, co
   }
 }
 
+// K5c -- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) over the flat fp32
+// gradient, as two launches with no atomics and no state a graph replay would have to reset:
+//   1. clip_sumsq_kernel: grid-stride float4 walk (scalar tail for n % 4), squares accumulated
+//      in fp64 per thread, folded across the wave by xor shuffles and across the four waves
+//      through LDS in wave order; one fp64 partial per workgroup.
+//   2. clip_scale_kernel: every workgroup sums all partials in the same fixed order, so all of
+//      them hold the same total = (float)sqrt(sum) and coef = min(1, max_norm / (total + 1e-6));
+//      each scales its share of g (skipped at coef == 1: a multiply by 1.0 is the identity) and
+//      workgroup 0 stores total, the norm before clipping.
+// The grid (hence the partition and the summation order) depends on n alone: the result is
+// bit-identical from call to call and from rank to rank.
+constexpr int CLIP_WG = 256;
+constexpr int CLIP_MAX_BLOCKS = 1024;  // one pass of the full grid covers 1024 * 256 * 4 floats
+
+static int clip_blocks(long n) {
+  const long blocks = (n + CLIP_WG * 4L - 1) / (CLIP_WG * 4L);
+  return (int)(blocks > CLIP_MAX_BLOCKS ? CLIP_MAX_BLOCKS : blocks < 1 ? 1 : blocks);
+}
+
+// sum of v over the workgroup, the same bits in every thread: butterfly within the wave (both
+// lanes of a pair add the same two values), then the waves' sums from LDS in wave order
+__device__ __forceinline__ double clip_block_sum(double v, double* lds) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = lds[0];
+#pragma unroll
+  for (int w = 1; w < CLIP_WG / 64; ++w) t += lds[w];
+  return t;
+}
+
+__global__ __launch_bounds__(CLIP_WG) void clip_sumsq_kernel(const float* __restrict__ g, long n,
+                                                              double* __restrict__ partials) {
+  __shared__ double lds[CLIP_WG / 64];
+  double acc = 0.0;
+  const long stride = (long)gridDim.x * CLIP_WG * 4;
+  for (long i = ((long)blockIdx.x * CLIP_WG + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      const float4 v = *reinterpret_cast<const float4*>(g + i);
+      const double a = v.x, b = v.y, c = v.z, d = v.w;
+      acc += a * a;
+      acc += b * b;
+      acc += c * c;
+      acc += d * d;
+    } else {
+      for (long k = i; k < n; ++k) {
+        const double a = g[k];
+        acc += a * a;
+      }
+    }
+  }
+  const double t = clip_block_sum(acc, lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(CLIP_WG) void clip_scale_kernel(float* __restrict__ g, long n, float max_norm,
+                                                              const double* __restrict__ partials,
+                                                              float* __restrict__ norm_out) {
+  __shared__ double lds[CLIP_WG / 64];
+  double acc = 0.0;
+  for (int p = threadIdx.x; p < (int)gridDim.x; p += CLIP_WG) acc += partials[p];  // launch 1 ran this grid
+  const float total = (float)sqrt(clip_block_sum(acc, lds));
+  const float coef = fminf(1.f, max_norm / (total + 1e-6f));
+  if (blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
+  if (coef == 1.f) return;
+  const long stride = (long)gridDim.x * CLIP_WG * 4;
+  for (long i = ((long)blockIdx.x * CLIP_WG + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      float4 v = *reinterpret_cast<float4*>(g + i);
+      v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
+      *reinterpret_cast<float4*>(g + i) = v;
+    } else {
+      for (long k = i; k < n; ++k) g[k] *= coef;
+    }
+  }
+}
+
 // f32 -> bf16 copy (shadow refresh after load / broadcast).
 __global__ __launch_bounds__(256) void to_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, long n) {
   const long stride = (long)gridDim.x * blockDim.x;
@@ -238,6 +316,26 @@ int sl_sgd_flat_lr(float* w, const float* g, float* mom, uint16_t* shadow, long 
   const FlatOpt o = {step, lr_tab, lr_n - 1, 0.f, mu, wd, gscale, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   hipLaunchKernelGGL(opt_flat_kernel<false>, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom,
                      static_cast<float*>(nullptr), shadow, n, o);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// fp64 partials sl_clip_grad_norm needs for a vector of n floats (its grid; 0 for n <= 0)
+int sl_clip_grad_partials(long n) { return n <= 0 ? 0 : clip_blocks(n); }
+
+// g *= min(1, max_norm / (||g||_2 + 1e-6)) over g[0, n) in place, *norm_out = ||g||_2 before
+// the scaling (max_norm = inf: measured, never scaled).  partials: scratch, rewritten whole by
+// every call.
+int sl_clip_grad_norm(float* g, long n, float max_norm, double* partials, int n_partials, float* norm_out,
+                      hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!g || ((uintptr_t)g & 15) || !partials || ((uintptr_t)partials & 7) || !norm_out) return -1;
+  if (!(max_norm > 0.f)) return -1;
+  const int blocks = clip_blocks(n);
+  if (n_partials < blocks) return -1;
+  hipLaunchKernelGGL(clip_sumsq_kernel, dim3(blocks), dim3(CLIP_WG), 0, stream, g, n, partials);
+  SL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(blocks), dim3(CLIP_WG), 0, stream, g, n, max_norm, partials, norm_out);
   SL_CHECK_LAUNCH();
   return 0;
 }

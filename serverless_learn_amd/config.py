@@ -64,6 +64,7 @@ class Config:
     lr_warmup_steps: int = 0           # linear warm-up over this many steps (0 = none)
     lr_decay_steps: int = 0            # step at which the decay ends (0 = max_steps)
     lr_min_ratio: float = 0.0          # the decay ends at lr_min_ratio * lr
+    clip_grad_norm: float = 0.0        # clip the aggregated gradient to this global L2 norm (0 = off, inf = measure)
     seed: int = 0
     checkpoint_every: int = 0          # steps between checkpoints (rank 0); 0 = off
     max_steps: int = 0                 # 0 = run until stopped

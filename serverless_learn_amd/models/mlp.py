@@ -28,7 +28,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.optim import OptSpec, adamw_update, lr_at, sgd_update  # noqa: F401  (the rules' semantics live there)
+# (the rules' semantics live there)
+from ..ops.optim import OptSpec, adamw_update, clip_grad_, lr_at, sgd_update  # noqa: F401
 from ..utils.graphs import GraphSlots
 
 D_IN = 784
@@ -166,8 +167,15 @@ class OptStateCPU:
         self.mom = torch.zeros_like(self.params) if (self.momentum > 0 or opt.adamw) else None
         self.v = torch.zeros_like(self.params) if opt.adamw else None
         self.opt_step = None if opt.plain else torch.zeros(1, dtype=torch.int32)
+        self._grad_norm = None
+
+    def grad_norm(self) -> float | None:
+        """The gradient's global L2 norm at the last step, before clipping (None: clipping off)."""
+        return self._grad_norm
 
     def _opt_update(self, g: torch.Tensor) -> None:
+        if self.opt.clips:
+            self._grad_norm = clip_grad_(g, self.opt.clip_grad_norm)
         if self.opt_step is None:
             sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
             return
@@ -353,6 +361,8 @@ class FusedMLPTrainer(GraphSlots):
             self.opt_step = torch.zeros(1, dtype=torch.int32, device=dev)
             self.opt_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
             self._build_lr_table()
+        self.clip_partials = self.clip_norm = None
+        self._init_clip()
         bf = torch.bfloat16
         # W1's shadow is fp16: layer 1 multiplies the exact pixels (fp16 1024 + u) and corrects the
         # offset with the W1 row sums, kept as 64-bit fixed-point partials (mlp_fused.hip, R1_BLK)
@@ -433,19 +443,33 @@ class FusedMLPTrainer(GraphSlots):
         tab = self.opt.lr_table()
         self.lr_tab = torch.from_numpy(tab).to(self.device) if tab is not None else None
 
+    def _init_clip(self) -> None:
+        """Gradient clipping's scratch (the workgroups' fp64 partial sums) and the norm it reports."""
+        if self.opt.clips and self.clip_norm is None:
+            from ..ops.optim import CLIP_KERNELS, clip_buffers, require_kernels
+
+            require_kernels(self.opt, *CLIP_KERNELS)
+            self.clip_partials, self.clip_norm = clip_buffers(N_PARAMS, self.device)
+
     def set_optimizer(self, **kw) -> None:
-        """Change optimizer hyper-parameters (OptSpec fields) of a step-counter rule: the
-        launches are rebuilt and the captured graphs dropped, as a new ``lr`` does.  The rule
-        itself (which state exists) is fixed at construction."""
+        """Change optimizer hyper-parameters (OptSpec fields; ``clip_grad_norm`` under any rule,
+        the others of a step-counter rule): the launches are rebuilt and the captured graphs
+        dropped, as a new ``lr`` does.  The rule itself (which state exists) is fixed at
+        construction."""
         import dataclasses
 
+        if self.opt.plain:  # a plain rule's lr / momentum / weight_decay live in the attributes
+            kw = {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay, **kw}
         new = dataclasses.replace(self.opt, **kw)
         if (new.adamw, new.plain) != (self.opt.adamw, self.opt.plain):
             raise ValueError("the optimizer rule is fixed at construction (build a new trainer)")
+        if new.clips and self.xgmi is not None:
+            raise ValueError("gradient clipping is not available with the xGMI exchange")
         self.opt = new
         self.lr, self.momentum, self.weight_decay = new.lr, new.momentum, new.weight_decay
         if not new.plain:
             self._build_lr_table()
+        self._init_clip()
         self.graph = None
         self._lkey = None
 
@@ -456,7 +480,8 @@ class FusedMLPTrainer(GraphSlots):
             self.set_optimizer(lr=hp[0], momentum=hp[1], weight_decay=hp[2])  # an attribute was assigned
         key = (self.x.data_ptr() if self.x is not None else 0, self.n_batches, self.grad_scale, self.lr,
                self.momentum, self.weight_decay, id(self.xgmi), bool(self.xgmi and self.xgmi.two_shot),
-               self.xgmi.inline_sync if self.xgmi is not None else None, None if self.opt.plain else self.opt)
+               self.xgmi.inline_sync if self.xgmi is not None else None, None if self.opt.plain else self.opt,
+               self.opt.clip_grad_norm)
         if getattr(self, "_lkey", None) == key:
             return self._lc
         n, p = self._n, self._n.ptr
@@ -487,6 +512,9 @@ class FusedMLPTrainer(GraphSlots):
                                 p(self.grad) if from_grad else None, p(self.grad) if grad_out else None,
                                 self.lr, self.momentum, self.weight_decay, *self.dw1_coeffs, mode, *ws,
                                 p(self.cursor) if bump else None, p(self.r1p))
+        if self.opt.clips:  # between the reduce and the update launches, on the real parameters only
+            lc["clip"] = n.Launch("sl_clip_grad_norm", p(self.grad), N_PARAMS, self.opt.clip_grad_norm,
+                                  p(self.clip_partials), self.clip_partials.numel(), p(self.clip_norm))
         if self.xgmi is not None:
             xg = self.xgmi
             # inline synchronisation: the reduce publishes the step, the update waits per workgroup
@@ -559,7 +587,11 @@ class FusedMLPTrainer(GraphSlots):
     def enable_xgmi(self, exchange) -> None:
         """Aggregate gradients through an :class:`~serverless_learn_amd.parallel.xgmi.XgmiExchange`
         (the slab reduction lands in this rank's exchange slot; the update kernel sums every
-        rank's slot over xGMI and applies SGD).  ``None`` switches back."""
+        rank's slot over xGMI and applies SGD).  ``None`` switches back.  Not with gradient
+        clipping: the summed gradient never exists before that update."""
+        if exchange is not None and self.opt.clips:
+            raise ValueError("gradient clipping is not available with the xGMI exchange "
+                             "(keep the process-group all-reduce)")
         if exchange is not None and exchange.payload_floats < self.n_pad:
             raise ValueError("exchange slot smaller than the parameter vector")
         self.xgmi = exchange
@@ -603,14 +635,22 @@ class FusedMLPTrainer(GraphSlots):
                 launch()
             ph.mark("exchange")  # slab reduction into the exchange slot + the step barrier(s)
             lc["xupdate"]()      # (the peers' slots are summed inside the update kernel)
-        elif self.allreduce is None:
+        elif self.allreduce is None and not self.opt.clips:
             self._sgd(2, from_grad=False, grad_out=False)
         else:
             self._sgd(1, from_grad=False, grad_out=True, bump=False)
-            self.allreduce(self.grad)
-            ph.mark("exchange")
+            if self.allreduce is not None:
+                self.allreduce(self.grad)
+                ph.mark("exchange")
+            if self.opt.clips:  # the whole norm before any weight moves: the fused slab update cannot clip
+                self._launches()["clip"]()
             self._sgd(2, from_grad=True, grad_out=False)
         ph.mark("update")
+
+    def grad_norm(self) -> float | None:
+        """The aggregated gradient's global L2 norm at the last step, before clipping (one float
+        read from the device); None with clipping off."""
+        return float(self.clip_norm[0]) if self.opt.clips else None
 
     def probe_step(self):
         """One eager training step with its phase boundaries recorded (utils/phases.py): returns

@@ -113,6 +113,11 @@ class FusedResNetTrainer(GraphSlots):
             tab = self.opt.lr_table()
             self.lr_tab = torch.from_numpy(tab).to(dev) if tab is not None else None
         self.grad = torch.zeros_like(self.params)
+        # gradient clipping: the workgroups' fp64 partial sums and the norm it reports
+        self.clip_partials = self.clip_norm = None
+        if self.opt.clips:
+            O.require_kernels(self.opt, *O.CLIP_KERNELS)
+            self.clip_partials, self.clip_norm = O.clip_buffers(n, dev)
         self.shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
         bns = list(spec.bns())
         rsz = {b.name: (K.rsum_floats(2 * b.c) + 3) // 4 * 4 for b in bns}  # 16-B aligned regions
@@ -424,6 +429,8 @@ class FusedResNetTrainer(GraphSlots):
         if self.allreduce is not None:
             self.allreduce(self.grad)
         self.phases.mark("exchange")
+        if self.opt.clips:  # on the aggregated gradient, before the unchanged update rule
+            self.O.clip_grad_norm_flat(self.grad, self.opt.clip_grad_norm, self.clip_partials, self.clip_norm)
         self._update()
         self.wt()
         self.K.cursor_bump(self.cursor)
@@ -443,6 +450,11 @@ class FusedResNetTrainer(GraphSlots):
             O.sgd_flat_lr(self.params, self.grad, self.mom, self.opt_step, self.lr_tab, self.momentum,
                           self.weight_decay, shadow=self.shadow)
         self.K.cursor_bump(self.opt_step)
+
+    def grad_norm(self) -> float | None:
+        """The aggregated gradient's global L2 norm at the last step, before clipping (one float
+        read from the device); None with clipping off."""
+        return float(self.clip_norm[0]) if self.opt.clips else None
 
     def step(self) -> None:
         if self.graph is not None:

@@ -7,6 +7,10 @@ Two rules: momentum SGD (``torch.optim.SGD``, dampening 0, no nesterov) and Adam
 learning rate from :func:`lr_at`: linear warm-up, then constant, linear or cosine decay.  On the
 GPU the step number is a device-resident counter, so a captured graph replays with a moving
 learning rate; the schedule reaches the kernels as an fp32 table of ``lr_at`` values.
+
+Either rule may be preceded by global-norm gradient clipping (``clip_grad_norm``,
+``torch.nn.utils.clip_grad_norm_``): :func:`clip_grad_` is its reference, and
+:func:`clip_grad_norm_flat` the two-launch kernel that a captured graph replays.
 """
 from __future__ import annotations
 
@@ -30,6 +34,8 @@ _ADAM = [N.F] * 7  # beta1, beta2, 1 - beta1, 1 - beta2, ln beta1, ln beta2, eps
 N.register("sl_adamw_flat", [N.P, N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, N.F, *_ADAM, N.P])
 N.register("sl_sgd_flat_lr", [N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, N.F, N.P])
 _STEP = [N.P, N.P, N.P, N.I]  # step, ticket, lr table, its length
+N.register("sl_clip_grad_partials", [N.L])
+N.register("sl_clip_grad_norm", [N.P, N.L, N.F, N.P, N.I, N.P, N.P])
 N.register("sl_mlp_opt", [N.I, N.P, N.P, N.P, N.P, N.I, N.L, N.P, N.F, N.F, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P,
                           N.P, N.P, *_STEP, *_ADAM, N.P])
 N.register("sl_mlp_opt_xgmi", [N.I, N.P, N.P, N.P, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.L, N.I,
@@ -78,6 +84,19 @@ def adamw_update(flat, m, v, grad, lr_t, beta1, beta2, eps, weight_decay, t):
     flat.addcdiv_(m, denom, value=-lr_t / (1.0 - beta1 ** t))
 
 
+CLIP_EPS = 1e-6  # torch.nn.utils.clip_grad_norm_'s constant
+
+
+def clip_grad_(g: torch.Tensor, max_norm: float) -> float:
+    """``torch.nn.utils.clip_grad_norm_`` over one flat gradient, in place: with ``total`` the
+    L2 norm of ``g`` (taken in float64), ``g *= min(1, max_norm / (total + 1e-6))``.  Returns
+    ``total``, the norm before clipping; ``max_norm = inf`` measures and never scales."""
+    total = float(torch.linalg.vector_norm(g.detach().double()))
+    coef = min(1.0, float(max_norm) / (total + CLIP_EPS))
+    g.mul_(coef)
+    return total
+
+
 @dataclass(frozen=True)
 class OptSpec:
     """The optimizer hyper-parameters a trainer is built with (its keyword arguments)."""
@@ -92,6 +111,7 @@ class OptSpec:
     lr_warmup_steps: int = 0
     lr_decay_steps: int = 0
     lr_min_ratio: float = 0.0
+    clip_grad_norm: float = 0.0  # max global L2 norm of the gradient (0: off; inf: measure only)
 
     def __post_init__(self):
         if self.optimizer not in OPTIMIZERS:
@@ -105,6 +125,12 @@ class OptSpec:
                              "(the worker defaults it to max_steps)")
         if self.adamw and not (0.0 < self.beta1 < 1.0 and 0.0 < self.beta2 < 1.0 and self.adam_eps > 0.0):
             raise ValueError("adamw needs 0 < beta1, beta2 < 1 and adam_eps > 0")
+        if not self.clip_grad_norm >= 0.0:  # negative or NaN
+            raise ValueError("clip_grad_norm must be >= 0 (0: off, inf: measure the norm only)")
+
+    @property
+    def clips(self) -> bool:
+        return self.clip_grad_norm > 0.0
 
     @property
     def adamw(self) -> bool:
@@ -159,17 +185,19 @@ class OptSpec:
             d.update(name=self.optimizer, beta1=self.beta1, beta2=self.beta2, eps=self.adam_eps,
                      weight_decay=self.weight_decay, schedule=self.lr_schedule, warmup_steps=self.lr_warmup_steps,
                      decay_steps=self.lr_decay_steps, min_ratio=self.lr_min_ratio)
+        if self.clips:
+            d["clip_grad_norm"] = self.clip_grad_norm
         return d
 
 
 def require_kernels(spec: OptSpec, *names: str) -> None:
-    """The step-counter rules need their entry points: an older kernel build (kept for A/B
-    runs of the SGD path) does not have them, and there is no fallback."""
+    """The step-counter rules and gradient clipping need their entry points: an older kernel
+    build (kept for A/B runs of the SGD path) does not have them, and there is no fallback."""
     lib = N.lib()
     missing = [n for n in names if not hasattr(lib, n)]
     if missing:
-        raise RuntimeError(f"optimizer {spec.optimizer!r} / lr_schedule {spec.lr_schedule!r} need "
-                           f"{', '.join(missing)}: not in this kernel library")
+        raise RuntimeError(f"optimizer {spec.optimizer!r} / lr_schedule {spec.lr_schedule!r} / clip_grad_norm "
+                           f"{spec.clip_grad_norm!r} need {', '.join(missing)}: not in this kernel library")
 
 
 # ---- flat kernels ----
@@ -211,3 +239,27 @@ def adamw_flat(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
 def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:
     assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16 and src.numel() == dst.numel()
     N.call("sl_to_bf16", N.ptr(src), N.ptr(dst), src.numel(), N.stream_ptr())
+
+
+CLIP_KERNELS = ("sl_clip_grad_norm", "sl_clip_grad_partials")
+
+
+def clip_partials(n: int) -> int:
+    """fp64 partials :func:`clip_grad_norm_flat` needs for a vector of ``n`` floats."""
+    return int(N.lib().sl_clip_grad_partials(int(n)))
+
+
+def clip_buffers(n: int, device) -> tuple:
+    """(partials, norm_out) for clipping a vector of ``n`` floats on ``device``."""
+    return (torch.zeros(max(1, clip_partials(n)), dtype=torch.float64, device=device),
+            torch.zeros(1, dtype=torch.float32, device=device))
+
+
+def clip_grad_norm_flat(g: torch.Tensor, max_norm: float, partials: torch.Tensor, norm_out: torch.Tensor) -> None:
+    """:func:`clip_grad_` on the device, in place, in two launches (csrc/kernels/elementwise.hip):
+    ``norm_out[0]`` receives the norm before clipping.  No host synchronisation and no state
+    between calls, so a captured graph replays it; bit-identical from call to call."""
+    assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and norm_out.dtype == torch.float32
+    N.call("sl_clip_grad_norm", N.ptr(g), g.numel(), float(max_norm), N.ptr(partials), partials.numel(),
+           N.ptr(norm_out), N.stream_ptr())

@@ -89,6 +89,7 @@ class Worker:
         self.view = {"epoch": 0, "peers": [], "rank": -1, "world": 0, "rendezvous": "", "resume_file": 0}
         self.trainer = None
         self.xgmi = None  # parallel.xgmi.XgmiExchange while an RCCL group of MLP workers is live
+        self._xgmi_skip_logged = False  # one xgmi_skipped event per worker (gradient clipping)
         self.gossip: GossipState | None = None
         backend = None if self.cfg.dp_backend == "auto" else self.cfg.dp_backend
         timeout = float(self.cfg.extra.get("dp_timeout_s", self.cfg.dp_timeout_s))
@@ -148,6 +149,8 @@ class Worker:
             kw.update(optimizer=c.optimizer, beta1=c.beta1, beta2=c.beta2, adam_eps=c.adam_eps,
                       lr_schedule=c.lr_schedule, lr_warmup_steps=c.lr_warmup_steps,
                       lr_decay_steps=c.lr_decay_steps or c.max_steps, lr_min_ratio=c.lr_min_ratio)
+        if c.clip_grad_norm != 0:  # under any rule (a negative value or NaN is refused by OptSpec)
+            kw.update(clip_grad_norm=c.clip_grad_norm)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
@@ -508,7 +511,17 @@ class Worker:
         if not (self.cfg.xgmi and t is not None and hasattr(t, "enable_xgmi") and self.device.type == "cuda"
                 and 2 <= self.group.world <= xgmi.MAX_WORLD and xgmi.enabled()):
             return False
-        return self.group.backend == "nccl" or os.environ.get("SL_XGMI_GLOO", "0") == "1"
+        if not (self.group.backend == "nccl" or os.environ.get("SL_XGMI_GLOO", "0") == "1"):
+            return False
+        if self.cfg.clip_grad_norm > 0:
+            # the fused exchange sums the peers' slots inside the update kernel: there is no summed
+            # gradient to clip before it.  The group keeps the process group's all-reduce.
+            if not self._xgmi_skip_logged:
+                self._xgmi_skip_logged = True
+                self.log.info("xgmi_skipped", reason="clip_grad_norm needs the summed gradient before the update",
+                              clip_grad_norm=self.cfg.clip_grad_norm)
+            return False
+        return True
 
     def _setup_xgmi(self) -> None:
         """MLP on a GPU group: aggregate through IPC-mapped exchange buffers over xGMI
@@ -866,6 +879,9 @@ class Worker:
                     # replica checksum for the elastic rehearsal (scripts/elastic_demo.py): a float64
                     # copy of every parameter and a device sync, so opt-in only
                     extra["param_sum"] = float(self.trainer.params.double().sum())
+                gn = self.trainer.grad_norm() if hasattr(self.trainer, "grad_norm") else None
+                if gn is not None:  # gradient clipping on: the last step's norm before clipping
+                    extra["grad_norm"] = round(gn, 6)
                 self.log.info("train", step=self.step, loss=round(st.loss, 4), acc=round(st.accuracy, 4),
                               samples_per_sec=round(self.rate, 1), epoch=self.group.epoch,
                               group_samples_per_sec=round(gm["samples_per_sec"], 1), group_world=gm["world"],

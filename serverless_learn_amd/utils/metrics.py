@@ -12,6 +12,7 @@ numeric fields of a few well-known events feed gauges / counters / histograms:
 * ``register_birth`` / ``deregister`` / ``evict`` -> ``sl_membership_epoch`` gauge
 * any ``epoch`` / ``world`` field -> ``sl_membership_epoch`` / ``sl_world_size``
 * ``train``'s step-time breakdown -> ``sl_step_phase_ms{phase}``, ``sl_exchange_gbps``
+* ``train``'s ``grad_norm`` (gradient clipping on) -> ``sl_grad_norm``
 
 Besides the log events, the transport reports every RPC it serves or makes (SURVEY.md §5.1,
 "per-RPC latency histograms"): ``sl_rpc_seconds{role,side,method,code}`` -- side ``server`` /
@@ -73,6 +74,8 @@ class Metrics:
                               ["role", "phase"], registry=r)
         self.exchange_gbps = Gauge("sl_exchange_gbps", "gradient exchange algorithm bandwidth of the probed step",
                                    ["role"], registry=r)
+        self.grad_norm = Gauge("sl_grad_norm", "global L2 norm of the last step's aggregated gradient before "
+                               "clipping (reported with gradient clipping on)", ["role"], registry=r)
 
     # ---- fed by the transport ---------------------------------------------------------
     def rpc(self, side: str, method: str, code: str, seconds: float) -> None:
@@ -116,6 +119,8 @@ class Metrics:
                         self.phase_ms.labels(role, ph[:-3]).set(fields[ph])
                 if isinstance(fields.get("exchange_gbps"), (int, float)):
                     self.exchange_gbps.labels(role).set(fields["exchange_gbps"])
+                if isinstance(fields.get("grad_norm"), (int, float)):
+                    self.grad_norm.labels(role).set(fields["grad_norm"])
             elif event == "job":
                 if isinstance(fields.get("samples_per_sec"), (int, float)):
                     self.job_rate.labels(role).set(fields["samples_per_sec"])
