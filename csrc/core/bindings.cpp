@@ -72,6 +72,33 @@ py::array decode_update(const py::buffer& msg, const std::string& dtype) {
   return out;
 }
 
+py::bytes encode_sparse_update_py(py::array_t<uint32_t, py::array::c_style> index,
+                                  py::array_t<float, py::array::c_style> value, uint64_t dense_len) {
+  if (index.ndim() != 1 || value.ndim() != 1 || index.size() != value.size())
+    throw std::invalid_argument("index and value must be 1-D arrays of the same length");
+  const size_t count = (size_t)index.size();
+  std::string s(sparse_update_encoded_size(count, dense_len), '\0');
+  encode_sparse_update(index.data(), value.data(), count, dense_len, (uint8_t*)s.data());
+  return py::bytes(s);
+}
+
+// ("dense", f64 array) or ("sparse", uint32 index, float32 value, dense_len)
+py::tuple decode_update_any(const py::buffer& msg) {
+  py::buffer_info info = contiguous(msg);
+  const uint8_t* p = (const uint8_t*)info.ptr;
+  const size_t len = (size_t)(info.size * info.itemsize);
+  const SparseView v = sparse_update_view(p, len);
+  if (v.dense_len == 0) return py::make_tuple("dense", decode_update(msg, "float64"));
+  const size_t count = sparse_update_validate(v);
+  py::array_t<uint32_t> index(count);
+  py::array_t<float> value(count);
+  if (count) {
+    std::memcpy(index.mutable_data(), v.index, 4 * count);
+    std::memcpy(value.mutable_data(), v.value, 4 * count);
+  }
+  return py::make_tuple("sparse", index, value, v.dense_len);
+}
+
 py::bytes encode_chunk_py(const py::buffer& data) {
   py::buffer_info info = contiguous(data);
   const size_t n = (size_t)(info.size * info.itemsize);
@@ -111,6 +138,10 @@ PYBIND11_MODULE(_slcore, m) {
     py::buffer_info i = contiguous(b);
     return update_count((const uint8_t*)i.ptr, (size_t)(i.size * i.itemsize));
   });
+  m.def("encode_sparse_update", &encode_sparse_update_py, py::arg("index"), py::arg("value"), py::arg("dense_len"),
+        "uint32 index, float32 value, dense length -> serialized sparse Update (fields 2-4)");
+  m.def("decode_update_any", &decode_update_any,
+        "serialized Update -> ('dense', f64 array) or ('sparse', index, value, dense_len)");
   m.def("encode_chunk", &encode_chunk_py);
   m.def("chunk_payload", &chunk_payload_py, "(offset, length) of Chunk.data inside the message");
   m.def("reference_dummy_file", &reference_dummy, "the reference file server's file 0 bytes");

@@ -87,6 +87,70 @@ void decode_update_f64(const uint8_t* buf, size_t len, double* dst, size_t cap) 
   });
 }
 
+size_t sparse_update_encoded_size(size_t count, uint64_t dense_len) {
+  size_t s = 0;
+  if (count) s += 2 * (1 + varint_size(4 * count) + 4 * count);  // proto3 omits empty bytes fields
+  if (dense_len) s += 1 + varint_size(dense_len);
+  return s;
+}
+
+void encode_sparse_update(const uint32_t* index, const float* value, size_t count, uint64_t dense_len, uint8_t* out) {
+  uint8_t* p = out;
+  if (count) {
+    *p++ = 0x12;
+    p = put_varint(p, 4 * (uint64_t)count);
+    std::memcpy(p, index, 4 * count);  // little-endian hosts, as the wire is
+    p += 4 * count;
+    *p++ = 0x1a;
+    p = put_varint(p, 4 * (uint64_t)count);
+    std::memcpy(p, value, 4 * count);
+    p += 4 * count;
+  }
+  if (dense_len) {
+    *p++ = 0x20;
+    put_varint(p, dense_len);
+  }
+}
+
+SparseView sparse_update_view(const uint8_t* buf, size_t len) {
+  SparseView v;
+  const uint8_t* p = buf;
+  const uint8_t* end = buf + len;
+  while (p < end) {
+    uint64_t key;
+    p = get_varint(p, end, &key);
+    const uint32_t fn = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
+    if ((fn == 2 || fn == 3) && wt == 2) {
+      uint64_t m;
+      p = get_varint(p, end, &m);
+      if ((uint64_t)(end - p) < m) throw WireError("truncated sparse field");
+      if (fn == 2) { v.index = p; v.index_bytes = (size_t)m; }
+      else { v.value = p; v.value_bytes = (size_t)m; }
+      p += m;
+    } else if (fn == 4 && wt == 0) {
+      p = get_varint(p, end, &v.dense_len);
+    } else {
+      p = skip_field(p, end, wt);
+    }
+  }
+  return v;
+}
+
+size_t sparse_update_validate(const SparseView& v) {
+  if (v.index_bytes % 4 || v.value_bytes % 4) throw WireError("sparse field length not a multiple of 4");
+  if (v.index_bytes != v.value_bytes) throw WireError("sparse_index and sparse_value differ in count");
+  const size_t count = v.index_bytes / 4;
+  uint64_t prev = 0;
+  for (size_t i = 0; i < count; ++i) {
+    uint32_t x;
+    std::memcpy(&x, v.index + 4 * i, 4);
+    if (i && x <= prev) throw WireError("sparse_index not strictly ascending");
+    if (x >= v.dense_len) throw WireError("sparse_index past sparse_len");
+    prev = x;
+  }
+  return count;
+}
+
 void chunk_payload(const uint8_t* buf, size_t len, size_t* off, size_t* n) {
   const uint8_t* p = buf;
   const uint8_t* end = buf + len;

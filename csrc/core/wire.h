@@ -57,6 +57,26 @@ size_t update_count(const uint8_t* buf, size_t len);                // number of
 void decode_update_f32(const uint8_t* buf, size_t len, float* dst, size_t cap);
 void decode_update_f64(const uint8_t* buf, size_t len, double* dst, size_t cap);
 
+// Sparse Update (additive fields; `delta` stays empty in a sparse message):
+//   sparse_index = 2, bytes: 0x12 varint(len) little-endian uint32[], strictly ascending
+//   sparse_value = 3, bytes: 0x1a varint(len) little-endian float32[], same count
+//   sparse_len   = 4, uint64: 0x20 varint, length of the dense vector the indices address
+// A message is sparse iff sparse_len is present and non-zero; an original parser skips all three.
+size_t sparse_update_encoded_size(size_t count, uint64_t dense_len);
+void encode_sparse_update(const uint32_t* index, const float* value, size_t count, uint64_t dense_len, uint8_t* out);
+
+struct SparseView {  // payloads inside the message buffer (last occurrence of a field wins)
+  const uint8_t* index = nullptr;
+  size_t index_bytes = 0;
+  const uint8_t* value = nullptr;
+  size_t value_bytes = 0;
+  uint64_t dense_len = 0;
+};
+SparseView sparse_update_view(const uint8_t* buf, size_t len);
+// Throws WireError on a byte length not divisible by 4, unequal counts, an index not strictly
+// ascending or an index >= dense_len; returns the entry count.
+size_t sparse_update_validate(const SparseView& v);
+
 // Chunk: returns (offset, length) of the data payload inside buf.
 void chunk_payload(const uint8_t* buf, size_t len, size_t* off, size_t* n);
 size_t chunk_encoded_size(size_t n);

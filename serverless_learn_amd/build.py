@@ -120,7 +120,9 @@ def _check_stubs(so: str) -> None:
 def build_core(force: bool = False) -> str:
     """Compile the C++ runtime (pybind11) against the HIP runtime API."""
     os.makedirs(NATIVE_DIR, exist_ok=True)
-    srcs = sorted(glob.glob(os.path.join(CORE_DIR, "*.cpp")))
+    # test_*.cpp are stand-alone programs (each has a main), built by their tests, not part of the module
+    srcs = sorted(s for s in glob.glob(os.path.join(CORE_DIR, "*.cpp"))
+                  if not os.path.basename(s).startswith("test_"))
     hdrs = sorted(glob.glob(os.path.join(CORE_DIR, "*.h")))
     if not srcs:
         return ""

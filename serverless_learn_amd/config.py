@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import math
 import os
 from dataclasses import dataclass, field
 
@@ -50,6 +51,8 @@ class Config:
     # --- worker training ---
     sync: str = "allreduce"            # allreduce | gossip | ps | none
     gossip_compat: bool = False        # reproduce the reference's alpha^2 echo exactly
+    gossip_topk: float = 0.0           # sync=gossip: send only this fraction of the parameters per message, the
+                                       # largest |m - o| (0 = dense; 0 < x <= 1; not with ps / simulate / compat)
     device: str = "auto"               # auto | cpu | cuda[:N]
     model: str = "mlp"                 # mlp | resnet18 | simulate (reference: vector += 1)
     batch: int = 1024
@@ -86,7 +89,29 @@ class Config:
                 setattr(cfg, f.name, _coerce(f, os.environ[key]))
         for k, v in overrides.items():
             setattr(cfg, k, v)
+        cfg.validate()
         return cfg
+
+    def __post_init__(self):
+        self.validate()
+
+    def validate(self) -> None:
+        """Refuse combinations no component implements (so far: the top-k sparse gossip's)."""
+        x = self.gossip_topk
+        if x == 0:
+            return
+        if not 0 < x <= 1:  # NaN included
+            raise ValueError(f"gossip_topk must be 0 (dense) or a fraction in (0, 1], got {x!r}")
+        if self.sync == "ps":
+            raise ValueError("gossip_topk: the master's parameter server stays dense (sync='ps')")
+        if self.model == "simulate":
+            raise ValueError("gossip_topk: the simulate model is growable and is never sparse")
+        if self.gossip_compat:
+            raise ValueError("gossip_topk: gossip_compat reproduces the reference's dense exchange byte for byte")
+
+    def gossip_k(self, n: int) -> int:
+        """Entries per sparse message for an n-parameter model (0 = dense)."""
+        return max(1, math.ceil(self.gossip_topk * n)) if self.gossip_topk > 0 else 0
 
     @property
     def gossip_interval(self) -> float:
@@ -130,4 +155,5 @@ def from_args(args: argparse.Namespace) -> Config:
         v = getattr(args, f.name, None)
         if v is not None:
             setattr(cfg, f.name, v)
+    cfg.validate()
     return cfg

@@ -19,6 +19,17 @@ delta-apply is then one fused HIP kernel, ``ops.gossip.delta_apply``: f64
 wire values in, f64 reply out, f32 model) or a float64/float32 CPU tensor.
 Callers serialize access with the training step (the reference mutated the
 vectors from three threads unlocked).
+
+Top-k sparse exchange (new, echo-free mode only): a message carries the at most
+``k`` entries of ``m - o`` of largest magnitude as (index, f32 value) pairs, and
+``o`` -- which tracks exactly what has been shared -- is the error feedback: it
+advances by what goes on the wire when it goes (``make_sparse_delta``; ``unsend``
+if the RPC fails) and by what is received (``absorb_sparse``), so whatever is not
+sent stays in ``m - o`` for a later message.  The server replies with its own top-k
+taken before mixing the request in (``serve_sparse``), so there is no echo to
+remove.  On the GPU the selection is ``ops.gossip.topk_select`` (an exact radix
+select, csrc/kernels/gossip_sparse.hip); the CPU path below is the same rule in
+numpy and is what the kernels are tested against.
 """
 from __future__ import annotations
 
@@ -46,6 +57,9 @@ class GossipState:
         self.exchanges = 0
         self.serves = 0  # server-side exchanges (each sets o = m)
         self._serves_at_send = 0
+        self._topk_ws = None   # device scratch of the sparse select, allocated once (ops.gossip.topk_workspace)
+        self._topk_ws_n = 0
+        self._topk_out = None
 
     # -- helpers -------------------------------------------------------------
     def _grow(self, n: int) -> None:
@@ -138,6 +152,106 @@ class GossipState:
             self.serves += 1
             self.exchanges += 1
             return reply
+
+
+    # -- top-k sparse exchange (echo-free only) -----------------------------------
+    # ``old`` is the error feedback: whatever is not sent stays in m - o and goes out later.
+    def _sparse_check(self) -> None:
+        if self.compat:
+            raise ValueError("sparse gossip is echo-free only: compat reproduces the reference byte for byte")
+        if self.growable:
+            raise ValueError("a growable model is never sparse")
+
+    def _check_index(self, index, value):
+        idx = np.ascontiguousarray(index, dtype=np.uint32).ravel()
+        val = np.ascontiguousarray(value, dtype=np.float32).ravel()
+        if idx.size != val.size:
+            raise ValueError("sparse index and value differ in count")
+        if idx.size and int(idx.max()) >= self.model.numel():
+            raise ValueError(f"sparse index {int(idx.max())} past the model's {self.model.numel()} elements")
+        return idx, val
+
+    def _add_at(self, t: torch.Tensor, idx: np.ndarray, inc: np.ndarray) -> None:
+        """t[idx] = dtype(double(t[idx]) + inc) on a CPU tensor (inc: float64)."""
+        i = torch.from_numpy(idx.astype(np.int64))
+        t[i] = (t[i].double() + torch.from_numpy(inc)).to(t.dtype)
+
+    def make_sparse_delta(self, k: int):
+        """The at most ``k`` entries of ``d = float32(double(m) - double(o))`` of largest magnitude:
+        ``(uint32 index ascending, float32 value)``, and ``o[index] += value`` in the same call.
+
+        The order is by the bit pattern of ``|d|`` as uint32, larger first (so non-finite values
+        first), equal magnitudes to the lower index; ``d == 0`` is never sent, so fewer than
+        ``k`` may come back.  ``o`` advances when the values go on the wire, not when the reply
+        arrives: a serve landing while the RPC is in flight can neither share the same progress
+        twice nor over-advance ``o``.  If the RPC fails, :meth:`unsend` takes it back."""
+        self._sparse_check()
+        with self.lock:
+            n = self.model.numel()
+            k = max(0, min(int(k), n))
+            if self._use_kernel():
+                from ..ops import gossip as gk
+
+                if self._topk_ws is None or self._topk_ws_n != n:
+                    self._topk_ws, self._topk_ws_n = gk.topk_workspace(n, self.model.device), n
+                if self._topk_out is None or self._topk_out.numel() < 4 + 2 * k:
+                    self._topk_out = gk.topk_out(k, self.model.device)
+                return gk.topk_select(self.model, self.old, k, self._topk_ws, self._topk_out)
+            d = (self.model.double() - self.old.double()).float().numpy()
+            idx = select_topk(d, k)
+            val = d[idx]
+            self._add_at(self.old, idx, val.astype(np.float64))
+            return idx, val
+
+    def unsend(self, index, value) -> None:
+        """Take back a :meth:`make_sparse_delta` whose RPC failed: ``o[index] -= value``.  Any
+        rounding left over is ordinary residual and goes out later."""
+        with self.lock:
+            idx, val = self._check_index(index, value)
+            if self._use_kernel():
+                from ..ops import gossip as gk
+
+                gk.scatter(self.model, self.old, idx, val, 1.0, sign_o_only=-1)
+            else:
+                self._add_at(self.old, idx, -val.astype(np.float64))
+
+    def absorb_sparse(self, index, value) -> None:
+        """``m[index] += a*value`` and the same to ``o``: what was received is common knowledge."""
+        self._sparse_check()
+        with self.lock:
+            idx, val = self._check_index(index, value)
+            if self._use_kernel():
+                from ..ops import gossip as gk
+
+                gk.scatter(self.model, self.old, idx, val, self.alpha)
+            else:
+                inc = self.alpha * val.astype(np.float64)
+                self._add_at(self.model, idx, inc)
+                self._add_at(self.old, idx, inc)
+            self.exchanges += 1
+
+    def serve_sparse(self, index_in, value_in, k: int, sparse_len: int | None = None):
+        """Server side: the reply is this side's own progress, taken BEFORE the incoming delta is
+        mixed in, so it carries no echo and the client removes none; then the delta is absorbed."""
+        self._sparse_check()
+        with self.lock:
+            if sparse_len is not None and int(sparse_len) != self.model.numel():
+                raise ValueError(f"sparse update addresses {int(sparse_len)} elements, model has {self.model.numel()}")
+            idx, val = self._check_index(index_in, value_in)
+            reply = self.make_sparse_delta(k)
+            self.absorb_sparse(idx, val)
+            return reply
+
+
+def select_topk(d: np.ndarray, k: int) -> np.ndarray:
+    """Indices (uint32, ascending) of the at most ``k`` non-zero entries of the float32 vector
+    ``d`` with the largest magnitude bits; equal magnitudes go to the lower index."""
+    key = np.ascontiguousarray(d, dtype=np.float32).view(np.uint32) & np.uint32(0x7FFFFFFF)
+    nz = np.flatnonzero(key)
+    if k < nz.size:
+        order = np.argsort(-key[nz].astype(np.int64), kind="stable")[:k]
+        nz = np.sort(nz[order])
+    return nz[:max(0, k)].astype(np.uint32)
 
 
 def exact_exchange(mA, oA, mB, oB, alpha=0.5, compat=True):

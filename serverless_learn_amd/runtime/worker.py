@@ -49,7 +49,8 @@ from ..utils import trace
 from ..utils.fault import FaultInjector
 from ..utils.log import Logger
 from ..utils.metrics import Metrics
-from ..wire.codec import chunk_payload, decode_update, encode_update, iter_chunks
+from ..wire.codec import (chunk_payload, decode_update, decode_update_any, encode_sparse_update, encode_update,
+                          iter_chunks)
 from .file_server import FILE_NUM_MD, FILE_SIZE_MD
 from .transport import Channels, RpcFailure, RpcServer, metadata_dict
 
@@ -76,6 +77,7 @@ class ChunkBroken(GroupBroken):
 class Worker:
     def __init__(self, addr: str, config: Config | None = None):
         self.cfg = config or Config.from_env()
+        self.cfg.validate()  # fields may have been set after construction
         self.addr_requested = addr
         self.addr = addr
         self.metrics = Metrics("worker")
@@ -262,16 +264,29 @@ class Worker:
         return fb.SerializeToString()
 
     def _exchange_updates(self, request: bytes, context) -> bytes:
-        delta = decode_update(request, "float64")
+        msg = decode_update_any(request)
+        sparse = msg[0] == "sparse"
         with self.train_lock:
             if self.gossip is None:
                 self._ensure_trainer()
             if self.gossip is None:  # allreduce/none worker asked to gossip: mix anyway
                 self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
-            with trace.span("gossip_serve", n=int(delta.size)):
-                reply = self.gossip.serve(delta)
+            out = None
+            if sparse:
+                # a sparse request is answered sparsely, with this worker's own k if it has one
+                _, index, value, n = msg
+                k = self.cfg.gossip_k(self.gossip.model.numel()) or max(1, int(index.size))
+                with trace.span("gossip_serve", n=int(n)) as sp:
+                    r_index, r_value = self.gossip.serve_sparse(index, value, k, sparse_len=n)
+                    out = encode_sparse_update(r_index, r_value, self.gossip.model.numel())
+                    sp.update(entries=int(index.size), wire_bytes=len(request) + len(out))
+            else:
+                delta = msg[1]
+                with trace.span("gossip_serve", n=int(delta.size)) as sp:
+                    reply = self.gossip.serve(delta)
+                    sp.update(entries=int(delta.size), wire_bytes=len(request) + 8 * int(reply.size))
             self._after_external_update()
-        return encode_update(reply)
+        return encode_update(reply) if out is None else out
 
     # ---- checkpoints -----------------------------------------------------------
     def _load_checkpoint(self, data: bytes) -> None:
@@ -944,7 +959,9 @@ class Worker:
             if not peers:  # the reference computes rand() % 0 here (worker.cc:200)
                 return False
             target, service = random.choice(peers), "Worker"
-        with trace.span("gossip", peer=target):
+        if self.cfg.gossip_topk > 0:
+            return self._gossip_sparse(target, service, md)
+        with trace.span("gossip", peer=target) as sp:
             with self.train_lock:
                 delta = self.gossip.make_delta()
             try:
@@ -953,8 +970,41 @@ class Worker:
                 self.log.warn("gossip_failed", peer=target, error=e.code.name if e.code else "")
                 return False
             reply = decode_update(raw, "float64")
+            sp.update(entries=int(delta.size), wire_bytes=8 * int(delta.size) + len(raw))
             with self.train_lock:
                 self.gossip.absorb(reply, delta)
+                self._after_external_update()
+        return True
+
+    def _gossip_sparse(self, target: str, service: str, md) -> bool:
+        """One top-k exchange: ``o`` advances when the values go on the wire and is taken back
+        if the RPC fails; the reply (the peer's own progress, no echo) is absorbed as it comes."""
+        g = self.gossip
+        with trace.span("gossip", peer=target) as sp:
+            with self.train_lock:
+                n = g.model.numel()
+                index, value = g.make_sparse_delta(self.cfg.gossip_k(n))
+            request = encode_sparse_update(index, value, n)
+            try:
+                raw = self.channels.unary(target, service, "ExchangeUpdates", request, metadata=md)
+            except RpcFailure as e:
+                with self.train_lock:
+                    g.unsend(index, value)
+                self.log.warn("gossip_failed", peer=target, error=e.code.name if e.code else "")
+                return False
+            sp.update(entries=int(index.size), wire_bytes=len(request) + len(raw))
+            try:
+                reply = decode_update_any(raw)
+                if reply[0] == "sparse" and int(reply[3]) != n:
+                    raise ValueError(f"sparse reply addresses {int(reply[3])} elements, model has {n}")
+            except ValueError:  # the peer took what was sent: o stays advanced, nothing is mixed in
+                self.log.warn("gossip_failed", peer=target, error="BAD_REPLY")
+                return False
+            with self.train_lock:
+                if reply[0] == "sparse":
+                    g.absorb_sparse(reply[1], reply[2])
+                else:  # an original or dense-only peer saw an empty delta and replied densely
+                    g.absorb(reply[1], np.zeros(0))
                 self._after_external_update()
         return True
 

@@ -29,14 +29,15 @@ def enabled() -> bool:
 
 @contextmanager
 def span(name: str, **args):
+    """Yields the span's ``args`` dict: values known only inside the span are added to it there."""
     if not _path:
-        yield
+        yield args
         return
     if _sync:
         _maybe_sync()
     t0 = time.perf_counter_ns()
     try:
-        yield
+        yield args
     finally:
         if _sync:
             _maybe_sync()

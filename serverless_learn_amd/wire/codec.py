@@ -1,6 +1,7 @@
 """Wire codec facade: hot messages through the C++ codec (csrc/core/wire.cpp).
 
-``Update`` (``repeated double delta = 1``, packed) and ``Chunk``
+``Update`` (``repeated double delta = 1``, packed; or its sparse form, the
+additive fields ``sparse_index = 2``, ``sparse_value = 3``, ``sparse_len = 4``) and ``Chunk``
 (``bytes data = 1``) are the two messages whose size scales with the model or
 the data; everything else goes through the
 descriptor-built protobuf classes in :mod:`serverless_learn_amd.proto.messages`.
@@ -24,6 +25,25 @@ def encode_update(values) -> bytes:
 
 def decode_update(msg: bytes, dtype: str = "float64") -> np.ndarray:
     return core().decode_update(msg, dtype)
+
+
+def encode_sparse_update(index, value, n: int) -> bytes:
+    """uint32 indices (strictly ascending), float32 values, dense length -> serialized sparse Update
+    (``sparse_index = 2``, ``sparse_value = 3``, ``sparse_len = 4``; ``delta`` stays empty)."""
+    idx = np.ascontiguousarray(index, dtype=np.uint32).ravel()
+    val = np.ascontiguousarray(value, dtype=np.float32).ravel()
+    if idx.size != val.size:
+        raise ValueError("sparse index and value differ in count")
+    return core().encode_sparse_update(idx, val, int(n))
+
+
+def decode_update_any(msg: bytes):
+    """``("dense", f64 array)`` or ``("sparse", uint32 index, float32 value, n)``.
+
+    A message is sparse iff ``sparse_len`` is present and non-zero.  Raises ``ValueError`` on a
+    sparse byte length not divisible by 4, unequal counts, an index not strictly ascending or an
+    index ``>= sparse_len``."""
+    return core().decode_update_any(msg)
 
 
 def encode_chunk(data) -> bytes:
