@@ -33,6 +33,10 @@
 //           whole step replays from a hipGraph without host work.
 //           (mlp_opt_kernel / mlp_opt_update_kernel: the same launches under AdamW or a
 //           scheduled lr, reading the device-resident optimizer step -- sgd_apply<RULE>)
+//
+// K_rows and K_wgrad read X either from the row-major u8 shard or (sl_mlp_rows_xt,
+// sl_mlp_wgrad_xt) from a copy of it tiled once per shard into 4 KB bricks of 64 rows x 64
+// columns (mlp_x_tile_kernel, XT_BRICK): the same bytes as whole, aligned cache lines.
 #include "common.h"
 #include "xgmi.h"
 
@@ -47,6 +51,10 @@ namespace {
 constexpr int D_IN = 784;   // input features (28x28)
 constexpr int D_INP = 832;  // layer-1 K padded to 13 chunks of 64 (w1h row stride)
 constexpr int NCHUNK = D_INP / 64;
+// Tiled form of the resident u8 shard (mlp_x_tile_kernel): xt[rows / 64][NCHUNK][64][64], a brick
+// (64 rows x 64 columns, row order) is 4 KB of contiguous memory, columns 784..831 are zero bytes.
+constexpr int XT_BRICK = 64 * 64;
+constexpr int XT_RB = NCHUNK * XT_BRICK;  // one 64-row block: 53,248 B
 constexpr int HID = 256;
 constexpr int NC = 10;
 constexpr int BM = 64;       // batch rows granularity (the rows kernel runs 64 or 128 per workgroup)
@@ -160,7 +168,7 @@ constexpr int ROW_STAMPS = 20;
 // (driver form +2.3 %, profiles/r05_prio; raising it after the softmax instead was neutral).
 
 struct MlpRowArgs {
-  const uint8_t* x;
+  const uint8_t* x;  // row-major [rows][784], or the tiled form (XT kernels)
   const uint8_t* y;
   const int* cursor;
   int n_batches, batch;
@@ -314,7 +322,9 @@ __device__ __forceinline__ void copy_part_buf(const uint16_t* src, int ld, __amd
 // (profiles/r04_rows128).  BM = 64 serves batches that are not a multiple of 128.  (An 8-wave
 // 256-row form, one workgroup per CU, measured 8 % slower and was removed: profiles/r03_big,
 // r04_rows128.)
-template <bool TRAIN, int BM>
+// XT: X comes from the tiled shard, so a wave's 64 16-B pieces of a chunk are 1 KB of contiguous,
+// line-aligned memory instead of 16 pieces of rows 784 B apart; same bytes, same arithmetic.
+template <bool TRAIN, int BM, bool XT>
 __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   constexpr int NWV = 4;               // waves per workgroup
   constexpr int MF = BM / 16;          // m-fragments per wave
@@ -402,10 +412,21 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
   // ---- layer 1: H1 = relu(X W1^T + b1), K = 832 streamed in 13 chunks of 64 ----
   const int xrow = tid >> 2, xcol = (tid & 3) * 16;
   const uint8_t* xg = a.x + (srow0 + xrow) * D_IN + xcol;
+  // XT: the workgroup's row blocks as a buffer; brick (p, c) is a constant offset, thread tid
+  // takes its bytes 16 tid .. 16 tid + 15 (row xrow, columns xcol .. xcol + 15)
+  static_assert(NT / 4 == 64 && BM % 64 == 0, "an X row pass is one 64-row block");
+  const auto xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.x) + (srow0 >> 6) * XT_RB, 0,
+                                                     (BM / 64) * XT_RB, 0x00020000);
   // X row pass p covers rows xrow + p * NT / 4
   auto xload = [&](int c, int p = 0) -> uint4 {
-    return (c * 64 + xcol < D_IN) ? *reinterpret_cast<const uint4*>(xg + (long)p * (NT / 4) * D_IN + c * 64)
-                                  : make_uint4(0, 0, 0, 0);
+    if constexpr (XT) {  // the pad columns are zero bytes in memory: no select
+      typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+      const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(xrs, tid * 16, (p * NCHUNK + c) * XT_BRICK, 0);
+      return make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+      return (c * 64 + xcol < D_IN) ? *reinterpret_cast<const uint4*>(xg + (long)p * (NT / 4) * D_IN + c * 64)
+                                    : make_uint4(0, 0, 0, 0);
+    }
   };
   auto zero_acc = [&]() {
 #pragma unroll
@@ -567,13 +588,22 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     static_assert(3 * BM * XLD <= 2 * REGB, "wide X ring must fit regions 0 and 1");
     const int xc2 = (tid & 3) * 32;
     const uint8_t* xg2 = a.x + (srow0 + xrow) * D_IN + xc2;
+    // XT: columns 128 c + xc2 .. + 31 lie in brick 2 c + xc2 / 64 (the thread's part is in xv2)
+    const int xv2 = (xc2 >> 6) * XT_BRICK + xrow * 64 + (xc2 & 63);
     uint4 xw[NCH][2];
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-        xw[c][h] = (c * 128 + xc2 + 16 * h < D_IN) ? *reinterpret_cast<const uint4*>(xg2 + c * 128 + 16 * h)
-                                                   : make_uint4(0, 0, 0, 0);
+      for (int h = 0; h < 2; ++h) {
+        if constexpr (XT) {
+          typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+          const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(xrs, xv2, 2 * c * XT_BRICK + 16 * h, 0);
+          xw[c][h] = (c * 128 + xc2 + 16 * h < D_IN) ? make_uint4(v[0], v[1], v[2], v[3]) : make_uint4(0, 0, 0, 0);
+        } else {
+          xw[c][h] = (c * 128 + xc2 + 16 * h < D_IN) ? *reinterpret_cast<const uint4*>(xg2 + c * 128 + 16 * h)
+                                                     : make_uint4(0, 0, 0, 0);
+        }
+      }
     auto xstore2 = [&](int c) {
       uint16_t* d = smem + (c % 3) * BM * XLD + xrow * XLD + xc2;
 #pragma unroll
@@ -1217,6 +1247,10 @@ constexpr int WG_MI = 8;  // 16-row A (dZ) fragments per wave
 constexpr int WG_NJ = 2;  // 16-column B fragments per wave
 constexpr int WG_NF = WG_MI + WG_NJ;       // fragments per wave per k-step
 
+// XT: problem 0's B operand is the tiled shard (a stage is one 64-row block, tile tn covers
+// bricks 2 tn and 2 tn + 1): every 16-B DMA piece lies in one cache line and a wave's piece
+// reads 8 whole 64-B rows of two bricks, not 8 x 128 B of rows 784 B apart.
+template <bool XT>
 __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[WG_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1260,9 +1294,15 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   {
     const int row = 8 * wave + (lane >> 3);
     const int c = wg_swz8(lane & 7, row);
-    const int col = min(n0 + c * 16, P.ldb - 16);  // columns >= 784 are don't-care columns of dW1
-    bsrc8 = static_cast<const uint8_t*>(P.b) + (xrow0 + st0 * 64 + row) * P.ldb + col;
+    if constexpr (XT) {
+      const int brick = min(2 * tn + (c >> 2), NCHUNK - 1);  // past the last brick: don't-care columns of dW1
+      bsrc8 = static_cast<const uint8_t*>(P.b) + ((xrow0 >> 6) + st0) * XT_RB + brick * XT_BRICK + row * 64 + (c & 3) * 16;
+    } else {
+      const int col = min(n0 + c * 16, P.ldb - 16);  // columns >= 784 are don't-care columns of dW1
+      bsrc8 = static_cast<const uint8_t*>(P.b) + (xrow0 + st0 * 64 + row) * P.ldb + col;
+    }
   }
+  const long bstep8 = XT ? XT_RB : 64 * P.ldb;  // u8 B: bytes per stage
   auto issue = [&](int st, auto u8_c) {  // stage st (relative to the slice) -> ring slot st % NS
     constexpr bool U8 = decltype(u8_c)::value;
     uint16_t* Ai = smem + (st % WG_NSLOT) * WG_SLOT;
@@ -1275,7 +1315,7 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
             (const __attribute__((address_space(1))) void*)(asrc[j] + (long)st * 64 * HID + h * 128),
             (SL_LDS void*)(Ai + h * WG_IMG + 4 * (2 * wave + j) * 128), 16, 0, 0);
     if constexpr (U8) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc8 + (long)st * 64 * P.ldb),
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc8 + (long)st * bstep8),
                                        (SL_LDS void*)(reinterpret_cast<uint8_t*>(Bi) + 8 * wave * 128), 16, 0, 0);
     } else {
 #pragma unroll
@@ -1996,9 +2036,43 @@ __global__ __launch_bounds__(UPD_NT) void mlp_opt_update_kernel(SgdArgs a, XgArg
 }
 
 // ---------------------------------------------------------------------------
+// Re-layout of the resident u8 shard, row-major [rows][784] -> xt[rows / 64][NCHUNK][64][64]
+// (XT_BRICK): once per shard, outside any graph.  Thread q writes 16-B piece q of the tiled
+// form (a wave stores 1 KB of contiguous memory; its loads are 16 pieces of 64 B).
+// ---------------------------------------------------------------------------
+constexpr int XTILE_NT = 256;
+__global__ __launch_bounds__(XTILE_NT) void mlp_x_tile_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                              long pieces) {
+  const long q = (long)blockIdx.x * XTILE_NT + threadIdx.x;
+  if (q >= pieces) return;
+  const long brick = q >> 8;  // 256 pieces per brick
+  const long rb = brick / NCHUNK;
+  const int c = (int)(brick - rb * NCHUNK);
+  const int r = (int)(q & 255) >> 2, col = c * 64 + ((int)q & 3) * 16;
+  static_assert(D_IN % 16 == 0, "a 16-B piece is all real columns or all pad");
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (col < D_IN) v = *reinterpret_cast<const uint4*>(src + (rb * 64 + r) * D_IN + col);
+  *reinterpret_cast<uint4*>(dst + q * 16) = v;
+}
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 extern "C" {
+
+// bytes of the tiled form of a shard of `rows` rows (a multiple of 64)
+long sl_mlp_x_tile_bytes(long rows) { return rows > 0 && rows % 64 == 0 ? rows / 64 * XT_RB : -1; }
+
+// src: row-major u8 [rows][784]; dst: sl_mlp_x_tile_bytes(rows) bytes, every one written
+int sl_mlp_x_tile(const uint8_t* src, uint8_t* dst, long rows, hipStream_t stream) {
+  if (!src || !dst || rows <= 0 || rows % 64 != 0) return -1;
+  if (((uintptr_t)src | (uintptr_t)dst) & 15) return -2;  // 16-B pieces
+  const long pieces = rows / 64 * XT_RB / 16;
+  hipLaunchKernelGGL(mlp_x_tile_kernel, dim3((unsigned)((pieces + XTILE_NT - 1) / XTILE_NT)), dim3(XTILE_NT), 0, stream,
+                     src, dst, pieces);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
 
 long sl_mlp_param_count() { return P_N; }
 
@@ -2038,14 +2112,15 @@ int sl_mlp_rows_bm(int batch) {
   return batch % 128 == 0 ? 128 : 64;
 }
 
-int sl_mlp_rows(const uint8_t* x, const uint8_t* y, const int* cursor, int n_batches, int batch,
-                const uint16_t* w1h, const uint16_t* w2h, const uint16_t* w3h, const uint16_t* w2th,
-                const uint16_t* w3th, const float* params, float xa, float xb,
-                float grad_scale, float dh1_scale,
-                uint16_t* h1, float* w3p, uint16_t* dh2, uint16_t* dh1,
-                float* loss, float* correct, float* logits, int train, const long long* r1p, unsigned* step_ctr,
-                hipStream_t stream) {
+static int mlp_rows_launch(bool xt, const uint8_t* x, const uint8_t* y, const int* cursor, int n_batches, int batch,
+                           const uint16_t* w1h, const uint16_t* w2h, const uint16_t* w3h, const uint16_t* w2th,
+                           const uint16_t* w3th, const float* params, float xa, float xb,
+                           float grad_scale, float dh1_scale,
+                           uint16_t* h1, float* w3p, uint16_t* dh2, uint16_t* dh1,
+                           float* loss, float* correct, float* logits, int train, const long long* r1p,
+                           unsigned* step_ctr, hipStream_t stream) {
   if (batch <= 0 || batch % BM != 0) return -1;
+  if (xt && ((uintptr_t)x & 15) != 0) return -2;  // 16-B buffer loads
   MlpRowArgs a;
   a.x = x; a.y = y; a.cursor = cursor; a.n_batches = n_batches > 0 ? n_batches : 1; a.batch = batch;
   a.w1h = w1h; a.w2h = w2h; a.w3h = w3h; a.w2th = w2th; a.w3th = w3th;
@@ -2059,16 +2134,35 @@ int sl_mlp_rows(const uint8_t* x, const uint8_t* y, const int* cursor, int n_bat
   a.step_ctr = train ? step_ctr : nullptr;
   if (train && (!h1 || !w3p || !dh2 || !dh1)) return -2;
   const int bm = sl_mlp_rows_bm(batch);
-  if (bm == 128) {
-    if (train) hipLaunchKernelGGL((mlp_rows_kernel<true, 128>), dim3(batch / 128), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((mlp_rows_kernel<false, 128>), dim3(batch / 128), dim3(256), 0, stream, a);
-  } else {
-    if (train) hipLaunchKernelGGL((mlp_rows_kernel<true, 64>), dim3(batch / 64), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((mlp_rows_kernel<false, 64>), dim3(batch / 64), dim3(256), 0, stream, a);
-  }
+  auto launch = [&](auto xt_c) {
+    constexpr bool XT = decltype(xt_c)::value;
+    if (bm == 128) {
+      if (train) hipLaunchKernelGGL((mlp_rows_kernel<true, 128, XT>), dim3(batch / 128), dim3(256), 0, stream, a);
+      else hipLaunchKernelGGL((mlp_rows_kernel<false, 128, XT>), dim3(batch / 128), dim3(256), 0, stream, a);
+    } else {
+      if (train) hipLaunchKernelGGL((mlp_rows_kernel<true, 64, XT>), dim3(batch / 64), dim3(256), 0, stream, a);
+      else hipLaunchKernelGGL((mlp_rows_kernel<false, 64, XT>), dim3(batch / 64), dim3(256), 0, stream, a);
+    }
+  };
+  if (xt) launch(std::true_type{});
+  else launch(std::false_type{});
   SL_CHECK_LAUNCH();
   return 0;
 }
+
+#define SL_MLP_ROWS_PARAMS                                                                                  \
+  const uint8_t *x, const uint8_t *y, const int *cursor, int n_batches, int batch, const uint16_t *w1h,     \
+      const uint16_t *w2h, const uint16_t *w3h, const uint16_t *w2th, const uint16_t *w3th,                 \
+      const float *params, float xa, float xb, float grad_scale, float dh1_scale, uint16_t *h1, float *w3p, \
+      uint16_t *dh2, uint16_t *dh1, float *loss, float *correct, float *logits, int train,                  \
+      const long long *r1p, unsigned *step_ctr, hipStream_t stream
+#define SL_MLP_ROWS_ARGS                                                                                      \
+  x, y, cursor, n_batches, batch, w1h, w2h, w3h, w2th, w3th, params, xa, xb, grad_scale, dh1_scale, h1, w3p, \
+      dh2, dh1, loss, correct, logits, train, r1p, step_ctr, stream
+// x: the resident u8 shard, row-major [n_batches * batch][784] ...
+int sl_mlp_rows(SL_MLP_ROWS_PARAMS) { return mlp_rows_launch(false, SL_MLP_ROWS_ARGS); }
+// ... or its tiled form (sl_mlp_x_tile of the first n_batches * batch rows)
+int sl_mlp_rows_xt(SL_MLP_ROWS_PARAMS) { return mlp_rows_launch(true, SL_MLP_ROWS_ARGS); }
 
 // Effective slice count for a batch: whole 64-row stages, equal-length
 // slices except the last (the slab array holds this many partial gradients).
@@ -2083,9 +2177,9 @@ int sl_mlp_wgrad_slices(int batch, int requested) {
 
 // x: the resident u8 shard [n_batches * batch][784]; the batch rows are the
 // ones the rows kernel used (cursor not yet bumped: mlp_sgd_kernel bumps it).
-int sl_mlp_wgrad(int batch, const uint8_t* x, const int* cursor, int n_batches, const uint16_t* h1,
-                 const uint16_t* dh2, const uint16_t* dh1, const float* w3p, int n_w3p, float* slab, int slices,
-                 long slab_stride, hipStream_t stream) {
+static int mlp_wgrad_launch(bool xt, int batch, const uint8_t* x, const int* cursor, int n_batches, const uint16_t* h1,
+                            const uint16_t* dh2, const uint16_t* dh1, const float* w3p, int n_w3p, float* slab,
+                            int slices, long slab_stride, hipStream_t stream) {
   // one partial row per rows-kernel workgroup (sl_mlp_rows_bm rows); n_w3p is the buffer's capacity
   if (!w3p || n_w3p < batch / 64) return -1;
   n_w3p = batch / sl_mlp_rows_bm(batch);
@@ -2110,9 +2204,21 @@ int sl_mlp_wgrad(int batch, const uint8_t* x, const int* cursor, int n_batches, 
   a.w3p = w3p; a.n_w3p = n_w3p;
   a.stamps = g_wg_stamps;
   if (((uintptr_t)x & 15) != 0 || ((uintptr_t)w3p & 15) != 0) return -2;  // 16-B pieces / float4 reads
-  hipLaunchKernelGGL(mlp_wgrad_kernel, dim3(base * slices), dim3(WG_NT), 0, stream, a);
+  if (xt) hipLaunchKernelGGL(mlp_wgrad_kernel<true>, dim3(base * slices), dim3(WG_NT), 0, stream, a);
+  else hipLaunchKernelGGL(mlp_wgrad_kernel<false>, dim3(base * slices), dim3(WG_NT), 0, stream, a);
   SL_CHECK_LAUNCH();
   return 0;
+}
+int sl_mlp_wgrad(int batch, const uint8_t* x, const int* cursor, int n_batches, const uint16_t* h1,
+                 const uint16_t* dh2, const uint16_t* dh1, const float* w3p, int n_w3p, float* slab, int slices,
+                 long slab_stride, hipStream_t stream) {
+  return mlp_wgrad_launch(false, batch, x, cursor, n_batches, h1, dh2, dh1, w3p, n_w3p, slab, slices, slab_stride, stream);
+}
+// x: the tiled form of the shard (sl_mlp_x_tile)
+int sl_mlp_wgrad_xt(int batch, const uint8_t* x, const int* cursor, int n_batches, const uint16_t* h1,
+                    const uint16_t* dh2, const uint16_t* dh1, const float* w3p, int n_w3p, float* slab, int slices,
+                    long slab_stride, hipStream_t stream) {
+  return mlp_wgrad_launch(true, batch, x, cursor, n_batches, h1, dh2, dh1, w3p, n_w3p, slab, slices, slab_stride, stream);
 }
 
 int sl_mlp_sgd(float* w, float* mom, const float* slab, int slices, long slab_stride, const float* grad_in,

@@ -7,7 +7,9 @@ RTLD_DEEPBIND, one trainer per build captures bench.py's 20-step graph while tha
 package's current library, and the arms then alternate rounds of pure graph replays: no process
 or box difference between the arms.  Prints per-arm medians, every round, and whether the arms'
 parameters ended bit-identical.
-Usage: python scripts/ab_mlp_libs.py ROUNDS STEPS name=/path/to/build.so name2=/path/to/other.so ..."""
+A path may end in @rows, @wgrad or @off: only that launch (or neither) reads X from the tiled
+shard, the other from the row-major one (the per-consumer arms of profiles/r11_xtile).
+Usage: python scripts/ab_mlp_libs.py ROUNDS STEPS name=/path/to/build.so name2=/path/to/other.so[@rows] ..."""
 import ctypes
 import json
 import os
@@ -27,6 +29,7 @@ x, y = make_mnist_like(B * 4, seed=0)
 xs, ys = torch.from_numpy(x), torch.from_numpy(y)
 trs = {}
 for name, path in arms:
+    path, _, only = path.partition("@")
     h = ctypes.CDLL(path, mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
     for fn in _native._SIGS:
         if hasattr(h, fn):
@@ -35,6 +38,15 @@ for name, path in arms:
     print(name, "sl_mlp_rows at", hex(ctypes.cast(h.sl_mlp_rows, ctypes.c_void_p).value), file=sys.stderr)
     tr = FusedMLPTrainer(batch=B, device="cuda:0")
     tr.load_shard(xs, ys)
+    if only:
+        xt, tr.xt = tr.xt, None
+        plain = dict(tr._launches())
+        tr.xt = xt
+        lc = tr._launches()  # cached under the tiled key: the swapped entries stay
+        for k in ("rows", "wgrad"):
+            if k != only:
+                lc[k] = plain[k]
+        print(name, {k: lc[k].entry for k in ("rows", "wgrad")}, file=sys.stderr)
     tr.capture(warmup=2, unroll=20)
     tr.steps(200)
     torch.cuda.synchronize()

@@ -391,6 +391,7 @@ class FusedMLPTrainer(GraphSlots):
         self.allreduce = None  # callable(grad_tensor) -> None, sums in place (RCCL)
         self.xgmi = None       # parallel.xgmi.XgmiExchange: all-reduce fused into the update (no RCCL)
         self.x = self.y = None
+        self.xt = None         # the shard in 64 x 64-byte bricks: what the training launches read
         self.n_batches = 1
         self.graph = None
         from ..utils.phases import PhaseProbe
@@ -422,6 +423,16 @@ class FusedMLPTrainer(GraphSlots):
         self.x = x.to(self.device, non_blocking=True).contiguous()
         self.y = y_u8.reshape(-1).to(self.device, non_blocking=True).to(torch.uint8).contiguous()
         self.n_batches = self.x.shape[0] // self.batch
+        # The training launches re-read the shard every step: laid out once in 4 KB bricks
+        # (xt[rows / 64][13][64][64], mlp_fused.hip XT_BRICK) every X access of theirs is whole
+        # aligned cache lines.  SL_MLP_XTILE=0 keeps them on the row-major shard (A/B, tests);
+        # older kernel builds, kept for A/B runs, have no tiled entry points.
+        self.xt = None
+        lib = self._n.lib()
+        if os.environ.get("SL_MLP_XTILE", "1") != "0" and hasattr(lib, "sl_mlp_x_tile"):
+            rows = self.n_batches * self.batch
+            self.xt = torch.empty(int(lib.sl_mlp_x_tile_bytes(rows)), dtype=torch.uint8, device=self.device)
+            self._n.call("sl_mlp_x_tile", self._n.ptr(self.x), self._n.ptr(self.xt), rows, self._n.stream_ptr())
         self.graph = None
 
     # ---- kernels ----
@@ -478,7 +489,8 @@ class FusedMLPTrainer(GraphSlots):
         hp = (self.lr, self.momentum, self.weight_decay)
         if not self.opt.plain and hp != (self.opt.lr, self.opt.momentum, self.opt.weight_decay):
             self.set_optimizer(lr=hp[0], momentum=hp[1], weight_decay=hp[2])  # an attribute was assigned
-        key = (self.x.data_ptr() if self.x is not None else 0, self.n_batches, self.grad_scale, self.lr,
+        key = (self.x.data_ptr() if self.x is not None else 0, self.xt.data_ptr() if self.xt is not None else 0,
+               self.n_batches, self.grad_scale, self.lr,
                self.momentum, self.weight_decay, id(self.xgmi), bool(self.xgmi and self.xgmi.two_shot),
                self.xgmi.inline_sync if self.xgmi is not None else None, None if self.opt.plain else self.opt,
                self.opt.clip_grad_norm)
@@ -486,17 +498,21 @@ class FusedMLPTrainer(GraphSlots):
             return self._lc
         n, p = self._n, self._n.ptr
         ws = (p(self.w1h), p(self.w2h), p(self.w2th), p(self.w3h), p(self.w3th))
+        # X from the tiled shard where there is one (load_shard): the same launches through their
+        # tiled entry points
+        xsrc, sfx = (self.xt, "_xt") if self.xt is not None else (self.x, "")
         lc = {
-            "rows": n.Launch("sl_mlp_rows", p(self.x), p(self.y), p(self.cursor), self.n_batches, self.batch,
+            "rows": n.Launch("sl_mlp_rows", p(xsrc), p(self.y), p(self.cursor), self.n_batches, self.batch,
                              p(self.w1h), p(self.w2h), p(self.w3h), p(self.w2th), p(self.w3th),
                              p(self.params), self.xa, self.xb, self.grad_scale, self.dh1_scale,
                              p(self.h1t), p(self.w3p), p(self.dh2t), p(self.dh1t),
                              p(self.loss), p(self.correct), None, 1, p(self.r1p),
                              # xGMI inline synchronisation: this launch advances the exchange's step id
-                             self.xgmi.ctl.data_ptr() if self.xgmi is not None and self.xgmi.inline_sync else None),
-            "wgrad": n.Launch("sl_mlp_wgrad", self.batch, p(self.x), p(self.cursor), self.n_batches,
+                             self.xgmi.ctl.data_ptr() if self.xgmi is not None and self.xgmi.inline_sync else None,
+                             entry="sl_mlp_rows" + sfx),
+            "wgrad": n.Launch("sl_mlp_wgrad", self.batch, p(xsrc), p(self.cursor), self.n_batches,
                               p(self.h1t), p(self.dh2t), p(self.dh1t), p(self.w3p), self.w3p.shape[0], p(self.slab),
-                              self.slices, self.slab_stride),
+                              self.slices, self.slab_stride, entry="sl_mlp_wgrad" + sfx),
         }
         for name, (mode, from_grad, grad_out, bump) in {"sgd": (2, False, False, True),
                                                         "reduce": (1, False, True, False),

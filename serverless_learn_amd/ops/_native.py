@@ -33,6 +33,11 @@ _SIGS: dict[str, list] = {
     "sl_mlp_slab_stride": [],
     "sl_mlp_rows": [P, P, P, I, I, P, P, P, P, P, P, F, F, F, F, P, P, P, P, P, P, P, I, P, P, P],
     "sl_mlp_wgrad": [I, P, P, I, P, P, P, P, I, P, I, L, P],
+    # the same two launches reading X from the tiled shard (sl_mlp_x_tile)
+    "sl_mlp_rows_xt": [P, P, P, I, I, P, P, P, P, P, P, F, F, F, F, P, P, P, P, P, P, P, I, P, P, P],
+    "sl_mlp_wgrad_xt": [I, P, P, I, P, P, P, P, I, P, I, L, P],
+    "sl_mlp_x_tile": [P, P, L, P],
+    "sl_mlp_x_tile_bytes": [L],
     "sl_mlp_wgrad_slices": [I, I],
     "sl_mlp_set_rows_bm": [I],
     "sl_conv_set_halo": [I],
@@ -48,7 +53,8 @@ _SIGS: dict[str, list] = {
     "sl_clock_probe": [P, P, I, P],
     "sl_comm_proxy": [P, P, L, I, P],
 }
-_RESTYPE = {"sl_mlp_param_count": ctypes.c_long, "sl_mlp_slab_stride": ctypes.c_long}
+_RESTYPE = {"sl_mlp_param_count": ctypes.c_long, "sl_mlp_slab_stride": ctypes.c_long,
+            "sl_mlp_x_tile_bytes": ctypes.c_long}
 
 
 def register(name: str, argtypes: list, restype=ctypes.c_int) -> None:
@@ -117,13 +123,20 @@ class Launch:
     and call them every step: the per-launch host cost drops to one ctypes
     call plus the current-stream lookup, which matters for the eager (non
     hipGraph) multi-GPU path where the host must stay ahead of ~30 us steps.
+
+    ``entry`` names another launcher of the same signature that does ``name``'s work from
+    differently laid-out inputs (``sl_mlp_rows`` / ``sl_mlp_rows_xt``): ``name`` stays the
+    launch's identity in the step, ``entry`` is the symbol called.
     """
 
-    __slots__ = ("name", "fn", "args")
+    __slots__ = ("name", "entry", "fn", "args")
 
-    def __init__(self, name: str, *args):
+    def __init__(self, name: str, *args, entry: str | None = None):
         self.name = name
-        fn = getattr(lib(), name)
+        self.entry = entry or name
+        if _SIGS[self.entry] != _SIGS[name]:
+            raise ValueError(f"{self.entry} does not have {name}'s signature")
+        fn = getattr(lib(), self.entry)
         self.fn = fn
         conv = []
         for a, t in zip(args, _SIGS[name]):
@@ -133,4 +146,4 @@ class Launch:
     def __call__(self, stream=None) -> None:
         rc = self.fn(*self.args, ctypes.c_void_p(stream_ptr(stream)))
         if rc != 0:
-            raise RuntimeError(f"{self.name} failed with code {rc}")
+            raise RuntimeError(f"{self.entry} failed with code {rc}")
