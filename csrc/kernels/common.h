@@ -1,8 +1,9 @@
 // Shared CDNA4 (gfx950) helpers for the serverless_learn_amd kernels.
 //
 // Everything here targets wave64 / MFMA 16x16x32 bf16.  Fragment maps
-// (cdna_hip_programming.md §3, verified with asymmetric operands in
-// tests/test_kernels_gpu.py):
+// (cdna_hip_programming.md §3; a wrong map moves or mixes output elements, which the
+// element-exact integer cases of tests/test_conv_exact_gpu.py catch for every convolution
+// kernel, and the logits / gradient references of tests/test_mlp_fused_gpu.py for the MLP):
 //   A frag  : lane l holds A[row = l&15][k = 8*(l>>4) + j], j = 0..7
 //   B frag  : lane l holds B[k = 8*(l>>4) + j][col = l&15]
 //   C/D     : lane l holds C[row = 4*(l>>4) + r][col = l&15], r = 0..3
@@ -174,6 +175,24 @@ __device__ __forceinline__ void rsum_add(float* rep, long i, float v) {
 }
 
 }  // namespace sl
+
+// Convolution kernel families, one bit each in the host-side record of what was launched since
+// the last clear (conv.hip sl_conv_kernels_seen; names in ops/cnn.py KERNEL_FAMILIES).  Tests
+// assert that a shape reached the kernel it is there for; nothing on the device reads this.
+enum SlConvFamily {
+  SL_KF_GEMM_64x64 = 0, SL_KF_GEMM_64x128, SL_KF_GEMM_128x64, SL_KF_GEMM_128x128,        // conv_gemm_kernel<.., false>
+  SL_KF_GEMM_T_64x64, SL_KF_GEMM_T_64x128, SL_KF_GEMM_T_128x64, SL_KF_GEMM_T_128x128,    // ... transposed gathers
+  SL_KF_BIG, SL_KF_BIG_T,            // conv_gemm_big_kernel
+  SL_KF_WIDE, SL_KF_WIDE_T,          // conv_gemm_wide_kernel<., 256>
+  SL_KF_WIDE128, SL_KF_WIDE128_T,    // conv_gemm_wide_kernel<., 128>
+  SL_KF_DGRAD_S2,                    // conv_dgrad_s2_kernel<128, 64, 3, 2>
+  SL_KF_DGRAD_S2_ALT,                // ... its SL_CONV_S2_WIDE tile shapes
+  SL_KF_WGRAD_64, SL_KF_WGRAD_64_LEAN, SL_KF_WGRAD_128, SL_KF_WGRAD_128_LEAN,  // conv_wgrad_kernel
+  SL_KF_WGRAD_BIG, SL_KF_WGRAD_BIG_LEAN,                                       // conv_wgrad_big_kernel
+  SL_KF_HALO_FWD_C64, SL_KF_HALO_FWD_C8, SL_KF_HALO_DGRAD, SL_KF_HALO_WGRAD,   // conv3x3_halo.hip
+  SL_KF_COUNT
+};
+extern "C" void sl_conv_note_kernel(int family);
 
 #define SL_CHECK_LAUNCH() \
   do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return (int)_e; } while (0)

@@ -1903,6 +1903,15 @@ static int fill_geom(ConvGeom& g, const uint16_t* src, int N, int SH, int SW, in
   return 0;
 }
 
+// Which kernel families (common.h SlConvFamily) were launched since the last clear: host-side
+// only, so a test can assert that its shape reached the kernel it is there for.
+static unsigned g_kernels_seen = 0;
+extern "C" void sl_conv_note_kernel(int family) { __atomic_fetch_or(&g_kernels_seen, 1u << family, __ATOMIC_RELAXED); }
+extern "C" int sl_conv_kernels_seen(int clear) {
+  return (int)(clear ? __atomic_exchange_n(&g_kernels_seen, 0u, __ATOMIC_RELAXED)
+                     : __atomic_load_n(&g_kernels_seen, __ATOMIC_RELAXED));
+}
+
 // 128-row tiles are used while they give at least this many workgroups;
 // SL_GEMM_SMALLM overrides it for A/B runs.
 static int gemm_smallm_tiles() {
@@ -1973,6 +1982,7 @@ static int launch_gemm(const ConvGeom& g, const ConvEpi& e, hipStream_t stream) 
     if (gemm_wide_enabled() && (long)grid.x >= 512) {
       hipLaunchKernelGGL((conv_gemm_wide_kernel<T, 256>), grid, dim3(256), 0, stream, g, e, p.tiles_n);
       SL_CHECK_LAUNCH();
+      sl_conv_note_kernel(T ? SL_KF_WIDE_T : SL_KF_WIDE);
       return 0;
     }
     if (gemm_wide_enabled() >= 2) {  // 128-row tiles, twice the grid (A/B: SL_GEMM_WIDE=2)
@@ -1980,10 +1990,12 @@ static int launch_gemm(const ConvGeom& g, const ConvEpi& e, hipStream_t stream) 
       dim3 grid128((unsigned)((long)tiles_m * p.tiles_n * g.ncls));
       hipLaunchKernelGGL((conv_gemm_wide_kernel<T, 128>), grid128, dim3(256), 0, stream, g, e, p.tiles_n);
       SL_CHECK_LAUNCH();
+      sl_conv_note_kernel(T ? SL_KF_WIDE128_T : SL_KF_WIDE128);
       return 0;
     }
     hipLaunchKernelGGL((conv_gemm_big_kernel<T>), grid, dim3(512), 0, stream, g, e, p.tiles_n);
     SL_CHECK_LAUNCH();
+    sl_conv_note_kernel(T ? SL_KF_BIG_T : SL_KF_BIG);
     return 0;
   }
   dim3 block(256);
@@ -1994,6 +2006,7 @@ static int launch_gemm(const ConvGeom& g, const ConvEpi& e, hipStream_t stream) 
   else if (p.BN == 128) hipLaunchKernelGGL((conv_gemm_kernel<64, 128, T, 3>), grid, block, 0, stream, g, e, p.tiles_n);
   else hipLaunchKernelGGL((conv_gemm_kernel<64, 64, T, 4>), grid, block, 0, stream, g, e, p.tiles_n);
   SL_CHECK_LAUNCH();
+  sl_conv_note_kernel((T ? SL_KF_GEMM_T_64x64 : SL_KF_GEMM_64x64) + (p.BM == 128 ? 2 : 0) + (p.BN == 128 ? 1 : 0));
   return 0;
 }
 
@@ -2127,6 +2140,7 @@ static int dgrad_launch(const ConvGeom& g, const uint16_t* dy, int N, int OH, in
     else if (wide == 3) hipLaunchKernelGGL((conv_dgrad_s2_kernel<64, 64, 4, 2>), grid, dim3(256), 0, stream, q, e, tiles_n, ae);
     else hipLaunchKernelGGL((conv_dgrad_s2_kernel<128, 64, 3, 2>), grid, dim3(256), 0, stream, q, e, tiles_n, ae);
     SL_CHECK_LAUNCH();
+    sl_conv_note_kernel(wide ? SL_KF_DGRAD_S2_ALT : SL_KF_DGRAD_S2);
     return 0;
   }
   if (((g_conv_phase && KH == 3) || add_even || even_only) && phase_ok) {
@@ -2399,9 +2413,11 @@ int sl_conv_wgrad(const uint16_t* x, int N, int H, int W, int C, const uint16_t*
     const bool slab = wgrad_use_slab(a, ws, ws_floats);
     if (SL_DETERMINISTIC && a.slices > 1 && !slab) return SL_NEED_WS;  // no order-dependent atomics
     if (slab) sl_wgrad_slab_acquire(ws, stream);
-    if (wgrad_lean_ok(a, 64, ldy)) hipLaunchKernelGGL(conv_wgrad_big_kernel<true>, dim3(tiles * a.slices), dim3(512), 0, stream, a);
+    const bool big_lean = wgrad_lean_ok(a, 64, ldy);
+    if (big_lean) hipLaunchKernelGGL(conv_wgrad_big_kernel<true>, dim3(tiles * a.slices), dim3(512), 0, stream, a);
     else hipLaunchKernelGGL(conv_wgrad_big_kernel<false>, dim3(tiles * a.slices), dim3(512), 0, stream, a);
     SL_CHECK_LAUNCH();
+    sl_conv_note_kernel(big_lean ? SL_KF_WGRAD_BIG_LEAN : SL_KF_WGRAD_BIG);
     return wgrad_finish(a, ws, ws_floats, stream, slab);
   }
   const int BMO = cout <= 64 ? 64 : 128;
@@ -2430,6 +2446,7 @@ int sl_conv_wgrad(const uint16_t* x, int N, int H, int W, int C, const uint16_t*
     else hipLaunchKernelGGL((conv_wgrad_kernel<128, WGRAD128_SLOTS, false>), grid, dim3(256), 0, stream, a);
   }
   SL_CHECK_LAUNCH();
+  sl_conv_note_kernel((BMO == 64 ? SL_KF_WGRAD_64 : SL_KF_WGRAD_128) + (lean ? 1 : 0));
   return wgrad_finish(a, ws, ws_floats, stream, slab);
 }
 

@@ -485,6 +485,7 @@ static int conv3x3_launch(const uint16_t* src, const uint16_t* w, int cin, int f
     else hipLaunchKernelGGL((conv3x3_kernel<64, false, false>), dim3(grid), dim3(NTF), 0, stream, a);
   }
   SL_CHECK_LAUNCH();
+  sl_conv_note_kernel(cin == 8 ? SL_KF_HALO_FWD_C8 : flip ? SL_KF_HALO_DGRAD : SL_KF_HALO_FWD_C64);
   return 0;
 }
 
@@ -853,6 +854,7 @@ static int conv3x3_wgrad_launch(const uint16_t* x, const uint16_t* dy, int ldy, 
   if (a.ws) sl_wgrad_slab_acquire(a.ws, stream);
   hipLaunchKernelGGL(conv3x3_wgrad_c64_kernel, dim3(grid), dim3(WNT), 0, stream, a);
   SL_CHECK_LAUNCH();
+  sl_conv_note_kernel(SL_KF_HALO_WGRAD);
   if (a.ws) {
     constexpr long units = 64L * 9 * HC / 4;
     hipStream_t rs = sl_wgrad_reduce_stream(stream);

@@ -48,6 +48,26 @@ N.register("sl_wgrad_side_join", [P, I])
 N.register("sl_conv3x3_c64_applicable", [I, I, I, I, I, I, I, I, I])
 N.register("sl_conv3x3_bnin_fwd", [P, P, I, I, P, I, P, P, P, P, P, P, P, F, F, F, P])
 N.register("sl_conv3x3_bnin_wgrad", [P, P, I, I, P, P, L, P, P, P, F, F, P])
+N.register("sl_conv_kernels_seen", [I])
+
+# bit i of sl_conv_kernels_seen = family i (csrc/kernels/common.h SlConvFamily, same order)
+KERNEL_FAMILIES = (
+    "gemm_64x64", "gemm_64x128", "gemm_128x64", "gemm_128x128",
+    "gemm_t_64x64", "gemm_t_64x128", "gemm_t_128x64", "gemm_t_128x128",
+    "big", "big_t", "wide", "wide_t", "wide128", "wide128_t",
+    "dgrad_s2", "dgrad_s2_alt",
+    "wgrad_64", "wgrad_64_lean", "wgrad_128", "wgrad_128_lean", "wgrad_big", "wgrad_big_lean",
+    "halo_fwd_c64", "halo_fwd_c8", "halo_dgrad", "halo_wgrad",
+)
+
+
+def conv_kernels_seen(clear: bool = False) -> frozenset:
+    """Names (:data:`KERNEL_FAMILIES`) of the convolution kernel families launched since the last
+    clear -- a host-side record kept by the launchers, so a test can assert which kernel a shape
+    reached.  ``clear`` resets the record after reading it."""
+    mask = int(N.lib().sl_conv_kernels_seen(1 if clear else 0))
+    assert mask >> len(KERNEL_FAMILIES) == 0, hex(mask)
+    return frozenset(name for i, name in enumerate(KERNEL_FAMILIES) if mask >> i & 1)
 
 p = N.ptr
 
