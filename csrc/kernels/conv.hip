@@ -36,6 +36,14 @@
 //                                  transposed with ds_read_b64_tr_b16)
 //   conv_wgrad_big_kernel          the same on 256 (co) x 128 (k) tiles, 8 waves
 //
+// The four forward / dgrad kernels differ in ring geometry, swizzle, fragment-read list and the
+// epilogue's pass structure.  What they share is defined once above them: tile and parity-class
+// placement (tile_place), row origins and tap shifts (row_gather, tap_shift), buffer resources
+// and per-tap lane masks (conv_rsrc, tap_masks), and the epilogue's statistics, fp32 store, bf16
+// staging, output offset and residual add (epi_stats, epi_store_f32, epi_stage, epi_chunk_off,
+// add_bf16x8).  hipcc's register allocation follows the source text, so a piece that changed a
+// kernel's VGPR count keeps its own text in that kernel, with a comment (profiles/r12_convparts).
+//
 // Forward epilogue options, all fused: per-channel BatchNorm statistics
 // (sum, sum of squares of the fp32 accumulator -> fp32 atomics), bias, fp32
 // output (logits), residual add (dgrad of a tensor that also feeds a skip).
@@ -149,11 +157,15 @@ __device__ __forceinline__ const uint16_t* gather_src(const ConvGeom& g, const P
 // (kh, kw, channel offset) are workgroup-uniform scalars and each lane only
 // offsets its row's precomputed pixel base.
 struct RowG {
-  long base;  // element offset of (n, ih0, iw0) [+ lane chunk], may be "negative" (padding)
+  long base;  // element offset of image n [+ lane chunk]
+  int b32;    // ... of pixel (n, ih0, iw0) [+ lane chunk], may be "negative" (padding); sources under 2^31 elements
   int ih0, iw0;
   bool ok;
 };
 
+// Row origin of a GEMM row: tap shift (dh, dw) reads source pixel (ih0 + dh, iw0 + dw) in the forward
+// gather, in phase mode and in the stride-1 transposed gather (ih = oh + pad - kh); at larger strides
+// the transposed sum is still to be divided by the stride (gather_tap).
 template <bool TRANSPOSED>
 __device__ __forceinline__ RowG row_gather(const ConvGeom& g, const Pix& p, int chunk8) {
   RowG r;
@@ -169,17 +181,32 @@ __device__ __forceinline__ RowG row_gather(const ConvGeom& g, const Pix& p, int 
     r.iw0 = p.ow + g.pad;
   }
   r.base = (long)p.n * g.SH * g.SW * g.SC + chunk8;
+  r.b32 = ((p.n * g.SH + r.ih0) * g.SW + r.iw0) * g.SC + chunk8;
   return r;
 }
 
+// Workgroup-uniform gather shift (dh, dw) of a stage's tap (tap0: the parity class's first entry in
+// the tap tables).
 template <bool TRANSPOSED>
-__device__ __forceinline__ const uint16_t* gather_tap(const ConvGeom& g, const RowG& r, int kh, int kw, int ch0) {
-  int ih, iw;
-  if (!TRANSPOSED || g.ph >= 0) {  // phase mode: (kh, kw) carry the parity class's (dh, dw)
-    ih = r.ih0 + kh;
-    iw = r.iw0 + kw;
+__device__ __forceinline__ void tap_shift(const ConvGeom& g, int tap0, int tap, int& dh, int& dw) {
+  if (TRANSPOSED && g.ph >= 0) {
+    dh = g.dh[tap0 + tap];
+    dw = g.dw[tap0 + tap];
   } else {
-    const int th = r.ih0 - kh, tw = r.iw0 - kw;
+    const int kh = (tap * g.kw_magic) >> 16, kw = tap - kh * g.KW;
+    dh = TRANSPOSED ? -kh : kh;
+    dw = TRANSPOSED ? -kw : kw;
+  }
+}
+
+template <bool TRANSPOSED>
+__device__ __forceinline__ const uint16_t* gather_tap(const ConvGeom& g, const RowG& r, int dh, int dw, int ch0) {
+  int ih, iw;
+  if (!TRANSPOSED || g.ph >= 0) {
+    ih = r.ih0 + dh;
+    iw = r.iw0 + dw;
+  } else {
+    const int th = r.ih0 + dh, tw = r.iw0 + dw;
     const int msk = (1 << g.s_shift) - 1;
     if ((th | tw) < 0 || ((th | tw) & msk)) return g_conv_zero;
     ih = th >> g.s_shift;
@@ -228,13 +255,158 @@ __device__ __forceinline__ short4_t ds_tr16(uint32_t a) {
 }
 
 // ---------------------------------------------------------------------------
+// Pieces shared by the forward / data-gradient GEMM kernels (conv_gemm, conv_gemm_big,
+// conv_gemm_wide, conv_dgrad_s2).  The kernels differ in ring geometry, swizzle, fragment-read
+// list and the epilogue's pass structure; what follows is everything else, once.
+// ---------------------------------------------------------------------------
+// 128-B LDS rows (64-deep stages): 16-B chunk c of row r at c ^ ((r >> 1) & 7)
+__device__ __forceinline__ int swz64(int c, int r) { return c ^ ((r >> 1) & 7); }
+// 64-B LDS rows (32-deep stages): chunk c of row r at c ^ g((r >> 2) & 3), g = {0, 2, 3, 1}
+__device__ __forceinline__ int swz32(int c, int r) { return c ^ ((0x78 >> (2 * ((r >> 2) & 3))) & 3); }
+
+// A workgroup's BM x BN tile and, where one launch covers several parity classes
+// (ConvGeom::ncls: equal blocks of the grid), its class.
+struct TilePos {
+  int m0, n0;
+  int K, ph, pw, tap0;  // of the class: reduction depth, parity, first entry of the tap tables
+  const uint16_t* add;  // ConvEpi::add, null where this class adds nothing
+};
+template <int BM, int BN>
+__device__ __forceinline__ TilePos tile_place(const ConvGeom& g, const ConvEpi& e, int tiles_n) {
+  const int logical0 = xcd_remap(blockIdx.x, gridDim.x);
+  const int per_cls = (int)gridDim.x / g.ncls;
+  const int cls = g.ncls > 1 ? logical0 / per_cls : 0;
+  const int logical = logical0 - cls * per_cls;
+  const int tm = logical / tiles_n, tn = logical - tm * tiles_n;
+  TilePos t;
+  t.m0 = tm * BM;
+  t.n0 = tn * BN;
+  t.K = g.cls_K[cls];
+  t.ph = g.cls_ph[cls];
+  t.pw = g.cls_pw[cls];
+  t.tap0 = g.cls_tap0[cls];
+  t.add = (g.add_cls0_only && cls) ? nullptr : e.add;
+  return t;
+}
+
+// Buffer resources over the gather source and the weight operand: an offset past the size (OOB)
+// loads zeros, which is the padding.  The host keeps both operands under 2 GB (plan_gemm).
+constexpr unsigned OOB = 0x80000000u;
+struct ConvRsrc {
+  __amdgpu_buffer_rsrc_t a, b;
+};
+__device__ __forceinline__ ConvRsrc conv_rsrc(const ConvGeom& g, const ConvEpi& e) {
+  return {__builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.src), 0, (int)((long)g.N * g.SH * g.SW * g.SC * 2),
+                                            0x00020000),
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(e.w), 0, (int)((long)e.ncols * g.wld * 2), 0x00020000)};
+}
+
+// Bit `tap` of mask[j]: row r[j] reads inside the image at that tap.  Computed once before the
+// k-loop, so a DMA piece costs an add, a bit test and a select per stage (~10 VALU with 64-bit
+// addresses and a zero-page select: profiles/r06_lean).  DEPTH: the stage depth (K / DEPTH stages).
+template <bool TRANSPOSED, int DEPTH, int PA>
+__device__ __forceinline__ void tap_masks(const ConvGeom& g, const TilePos& t, int cps_shift, const RowG (&r)[PA],
+                                          unsigned (&mask)[PA]) {
+#pragma unroll
+  for (int j = 0; j < PA; ++j) mask[j] = 0;
+#pragma unroll 1
+  for (int tap = 0; tap < (t.K / DEPTH) >> cps_shift; ++tap) {
+    int dh, dw;
+    tap_shift<TRANSPOSED>(g, t.tap0, tap, dh, dw);
+#pragma unroll
+    for (int j = 0; j < PA; ++j) {
+      const bool v = r[j].ok && (unsigned)(r[j].ih0 + dh) < (unsigned)g.SH && (unsigned)(r[j].iw0 + dw) < (unsigned)g.SW;
+      mask[j] |= (unsigned)v << tap;
+    }
+  }
+}
+
+// Epilogue pieces on a wave's MT x NT accumulator tiles (C/D map of common.h).  row0 / col0: the
+// wave's first row and column in the GEMM; lr = lane & 15, lg = lane >> 4.
+// Per-channel BatchNorm sums (sum, sum of squares) over the wave's rows; rows >= M are exact zeros.
+template <int MT, int NT>
+__device__ __forceinline__ void epi_stats(const ConvEpi& e, const floatx4_t (&acc)[MT][NT], int col0, int lr, int lg) {
+  float* rep = rsum_replica(e.stats, 2 * e.ncols);
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    float s = 0.f, q = 0.f;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = acc[i][j][r];
+        s += v;
+        q += v * v;
+      }
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    q += __shfl_xor(q, 16);
+    q += __shfl_xor(q, 32);
+    const int col = col0 + j * 16 + lr;
+    if (lg == 0 && col < e.ncols) {
+      rsum_add(rep, col, s);
+      rsum_add(rep, e.ncols + col, q);
+    }
+  }
+}
+// fp32 output (+ bias)
+template <int MT, int NT>
+__device__ __forceinline__ void epi_store_f32(const ConvEpi& e, int M, const floatx4_t (&acc)[MT][NT], int row0, int col0,
+                                              int lr, int lg) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int col = col0 + j * 16 + lr;
+      if (col >= e.ncols) continue;
+      const float b = e.bias ? e.bias[col] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = row0 + i * 16 + 4 * lg + r;
+        if (row < M) e.yf[(long)row * e.ncols + col] = acc[i][j][r] + b;
+      }
+    }
+}
+// bf16 tile (+ bias) into the LDS staging image Cs (row stride LD).  rl0 / cl0: the wave's first
+// row and column in the tile; n0: the tile's first column.
+template <int LD, int MT, int NT>
+__device__ __forceinline__ void epi_stage(const ConvEpi& e, const floatx4_t (&acc)[MT][NT], uint16_t* Cs, int rl0, int cl0,
+                                          int n0, int lr, int lg) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int cl = cl0 + j * 16 + lr;
+      const float b = (e.bias && n0 + cl < e.ncols) ? e.bias[n0 + cl] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Cs[(rl0 + i * 16 + 4 * lg + r) * LD + cl] = f2bf(acc[i][j][r] + b);
+    }
+}
+// Element offset in the output of the 8-column chunk at (GEMM row, col).  Phase mode: the row is pixel
+// (n, i, j) of the parity-class grid and lands at pixel (n, 2i + ph, 2j + pw) of the full output.
+template <bool TRANSPOSED>
+__device__ __forceinline__ long epi_chunk_off(const ConvGeom& g, const ConvEpi& e, const TilePos& t, int row, int col) {
+  long orow = row;
+  if (TRANSPOSED && g.ph >= 0) {
+    const Pix q = decode_pix(g, row);
+    orow = ((long)q.n * g.FH + 2 * q.oh + t.ph) * g.FW + 2 * q.ow + t.pw;
+  }
+  return orow * e.ldy + col;
+}
+// v + a on 8 bf16 (the residual add)
+__device__ __forceinline__ short8_t add_bf16x8(short8_t v, const short8_t& a) {
+#pragma unroll
+  for (int t = 0; t < 8; ++t) v[t] = (short)f2bf(bf2f((uint16_t)v[t]) + bf2f((uint16_t)a[t]));
+  return v;
+}
+
+// ---------------------------------------------------------------------------
 // Forward / dgrad implicit GEMM.  256 threads = 2x2 waves; each wave owns a
 // (BM/2) x (BN/2) sub-tile = (BM/32) x (BN/32) MFMA 16x16 tiles.  Operand
 // images are [rows][64 k] bf16 (128-B rows); 16-B chunk c of row r sits at
 // position c ^ ((r >> 1) & 7), which makes the 16 rows of a fragment read hit
 // 16 distinct bank groups.  One DMA piece = 8 rows = 1 KB.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int swz64(int c, int r) { return c ^ ((r >> 1) & 7); }
 
 template <int BM, int BN, bool TRANSPOSED, int NSLOT>
 __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e, int tiles_n) {
@@ -248,15 +420,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lg = lane >> 4;
-  const int logical0 = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_cls = (int)gridDim.x / g.ncls;  // merged parity classes: equal grid blocks
-  const int cls = g.ncls > 1 ? logical0 / per_cls : 0;
-  const int logical = logical0 - cls * per_cls;
-  const int gK = g.cls_K[cls], gph = g.cls_ph[cls], gpw = g.cls_pw[cls], tap0 = g.cls_tap0[cls];
-  const uint16_t* eadd = (g.add_cls0_only && cls) ? nullptr : e.add;
-  const int tm = logical / tiles_n, tn = logical - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const TilePos tp = tile_place<BM, BN>(g, e, tiles_n);
+  const int m0 = tp.m0, n0 = tp.n0;
   const int wm = wave >> 1, wn = wave & 1;
+  const bool phase = TRANSPOSED && g.ph >= 0;
 
   // DMA map: piece j of this wave covers rows 8 (wave * P + j) .. +7; lane -> row + lane / 8,
   // LDS position lane % 8 <- source chunk swz64(lane % 8, row).
@@ -275,12 +442,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
   // cheap path: transposed gathers only at stride 1 or in phase mode; 32-bit offsets
   const bool cheap = (!TRANSPOSED || g.ph >= 0 || g.stride == 1) &&
                      (long)g.N * g.SH * g.SW * g.SC < (1L << 31);
-  int rb32[PA];
-#pragma unroll
-  for (int j = 0; j < PA; ++j) {
-    int ih0 = ra[j].ih0, iw0 = ra[j].iw0;
-    rb32[j] = ((pa[j].n * g.SH + ih0) * g.SW + iw0) * g.SC + ca[j] * 8;
-  }
   const uint16_t* pb[PB];
   int cb[PB];
 #pragma unroll
@@ -294,36 +455,24 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
     uint16_t* As = smem + (kt % NSLOT) * SLOT;
     uint16_t* Bs = As + BM * BK;
     int kb = kt * BK;  // B-operand column of this stage
-    if (uniform_tap && cheap) {
-      // 32-bit row bases + a workgroup-uniform tap offset (as conv_gemm_big_kernel)
+    if (uniform_tap) {
       const int tap = kt >> cps_shift, ch0 = (kt & ((1 << cps_shift) - 1)) * 64;
       int dh, dw;
-      if (TRANSPOSED && g.ph >= 0) {
-        dh = g.dh[tap0 + tap];
-        dw = g.dw[tap0 + tap];
-        kb = g.tapw[tap0 + tap] * g.SC + ch0;
+      tap_shift<TRANSPOSED>(g, tp.tap0, tap, dh, dw);
+      if (phase) kb = g.tapw[tp.tap0 + tap] * g.SC + ch0;
+      if (cheap) {
+        // 32-bit row bases + a workgroup-uniform tap offset (as conv_gemm_big_kernel)
+        const int soff = (dh * g.SW + dw) * g.SC + ch0;
+#pragma unroll
+        for (int j = 0; j < PA; ++j) {
+          const bool v = ra[j].ok && (unsigned)(ra[j].ih0 + dh) < (unsigned)g.SH && (unsigned)(ra[j].iw0 + dw) < (unsigned)g.SW;
+          glds16(v ? g.src + (ra[j].b32 + soff) : g_conv_zero, (SL_LDS void*)(As + (wave * PA + j) * 8 * BK));
+        }
       } else {
-        const int kh = (tap * g.kw_magic) >> 16, kw = tap - kh * g.KW;
-        dh = TRANSPOSED ? -kh : kh;
-        dw = TRANSPOSED ? -kw : kw;
-      }
-      const int soff = (dh * g.SW + dw) * g.SC + ch0;
 #pragma unroll
-      for (int j = 0; j < PA; ++j) {
-        const bool v = ra[j].ok && (unsigned)(ra[j].ih0 + dh) < (unsigned)g.SH && (unsigned)(ra[j].iw0 + dw) < (unsigned)g.SW;
-        glds16(v ? g.src + (rb32[j] + soff) : g_conv_zero, (SL_LDS void*)(As + (wave * PA + j) * 8 * BK));
+        for (int j = 0; j < PA; ++j)
+          glds16(gather_tap<TRANSPOSED>(g, ra[j], dh, dw, ch0), (SL_LDS void*)(As + (wave * PA + j) * 8 * BK));
       }
-    } else if (uniform_tap) {
-      const int tap = kt >> cps_shift, ch0 = (kt & ((1 << cps_shift) - 1)) * 64;
-      int kh = (tap * g.kw_magic) >> 16, kw = tap - kh * g.KW;
-      if (TRANSPOSED && g.ph >= 0) {
-        kh = g.dh[tap0 + tap];
-        kw = g.dw[tap0 + tap];
-        kb = g.tapw[tap0 + tap] * g.SC + ch0;
-      }
-#pragma unroll
-      for (int j = 0; j < PA; ++j)
-        glds16(gather_tap<TRANSPOSED>(g, ra[j], kh, kw, ch0), (SL_LDS void*)(As + (wave * PA + j) * 8 * BK));
     } else {
 #pragma unroll
       for (int j = 0; j < PA; ++j)
@@ -332,7 +481,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
 #pragma unroll
     for (int j = 0; j < PB; ++j) {
       const int k0 = kt * BK + cb[j] * 8;
-      glds16((pb[j] && k0 < gK) ? pb[j] + (kb + cb[j] * 8) : g_conv_zero, (SL_LDS void*)(Bs + (wave * PB + j) * 8 * BK));
+      glds16((pb[j] && k0 < tp.K) ? pb[j] + (kb + cb[j] * 8) : g_conv_zero, (SL_LDS void*)(Bs + (wave * PB + j) * 8 * BK));
     }
   };
 
@@ -358,7 +507,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = zero4();
 
-  const int nk = (gK + BK - 1) / BK;
+  const int nk = (tp.K + BK - 1) / BK;
   for (int kt = 0; kt < NSLOT - 1 && kt < nk; ++kt) issue(kt);
   for (int kt = 0; kt < nk; ++kt) {
     vmcnt_stages<PS>(min(NSLOT - 2, nk - 1 - kt));
@@ -384,58 +533,12 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
   __syncthreads();
 
   // ---- epilogue ----
-  if (e.stats) {
-    float* rep = rsum_replica(e.stats, 2 * e.ncols);
-    // per-column partial sums over this wave's rows (rows >= M are exact zeros)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      float s = 0.f, q = 0.f;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = acc[i][j][r];
-          s += v;
-          q += v * v;
-        }
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      const int col = n0 + wn * (BN / 2) + j * 16 + lr;
-      if (lg == 0 && col < e.ncols) {
-        rsum_add(rep, col, s);
-        rsum_add(rep, e.ncols + col, q);
-      }
-    }
-  }
-  if (e.yf) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int col = n0 + wn * (BN / 2) + j * 16 + lr;
-        if (col >= e.ncols) continue;
-        const float b = e.bias ? e.bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = m0 + wm * (BM / 2) + i * 16 + 4 * lg + r;
-          if (row < g.M) e.yf[(long)row * e.ncols + col] = acc[i][j][r] + b;
-        }
-      }
-  }
+  if (e.stats) epi_stats(e, acc, n0 + wn * (BN / 2), lr, lg);
+  if (e.yf) epi_store_f32(e, g.M, acc, m0 + wm * (BM / 2), n0 + wn * (BN / 2), lr, lg);
   if (!e.y) return;
   // bf16 tile through LDS -> coalesced 16-B row stores (+ bias, + residual, + fused BN backward)
   uint16_t* Cs = smem;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int cl = wn * (BN / 2) + j * 16 + lr;
-      const float b = (e.bias && n0 + cl < e.ncols) ? e.bias[n0 + cl] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Cs[(wm * (BM / 2) + i * 16 + 4 * lg + r) * CS_LD + cl] = f2bf(acc[i][j][r] + b);
-    }
+  epi_stage<CS_LD>(e, acc, Cs, wm * (BM / 2), wn * (BN / 2), n0, lr, lg);
   // A thread's 16-B chunks: column chunk tid % CPR of rows tid / CPR + i * (256 / CPR).  Their
   // residual / BN operands are loaded here, all in flight under the staging barrier.
   constexpr int CPR = BN / 8;  // 16-B chunks per row
@@ -450,14 +553,9 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
 #pragma unroll
   for (int it = 0; it < EIT; ++it) {
     const int row = m0 + tid / CPR + it * (256 / CPR);
-    long orow = row;  // phase mode: parity-class pixel -> full-output pixel
-    if (TRANSPOSED && g.ph >= 0) {
-      const Pix q = decode_pix(g, row);
-      orow = ((long)q.n * g.FH + 2 * q.oh + gph) * g.FW + 2 * q.ow + gpw;
-    }
-    eoff[it] = orow * e.ldy + col;
+    eoff[it] = epi_chunk_off<TRANSPOSED>(g, e, tp, row, col);
     const bool ok = row < g.M && full;
-    if (ok && eadd) ea[it] = ld8(eadd + eoff[it]);
+    if (ok && tp.add) ea[it] = ld8(tp.add + eoff[it]);
     if (ok && bnb) bnb_load(e.bn, eoff[it], ebn[it]);
   }
   BnbAcc bacc;
@@ -471,16 +569,13 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvGeom g, ConvEpi e
     short8_t v = *reinterpret_cast<const short8_t*>(Cs + rl * CS_LD + cc);
     uint16_t* dst = e.y + eoff[it];
     if (full) {
-      if (eadd) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = (short)f2bf(bf2f((uint16_t)v[t]) + bf2f((uint16_t)ea[it][t]));
-      }
+      if (tp.add) v = add_bf16x8(v, ea[it]);
       if (bnb) bnb_chunk(e.bn, ebn[it], v, msc, msh, bacc);
       *reinterpret_cast<short8_t*>(dst) = v;
     } else {
       for (int t = 0; t < 8 && col + t < e.ncols; ++t) {
         float f = bf2f((uint16_t)v[t]);
-        if (eadd) f += bf2f(eadd[eoff[it] + t]);
+        if (tp.add) f += bf2f(tp.add[eoff[it] + t]);
         dst[t] = f2bf(f);
       }
     }
@@ -519,41 +614,23 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lg = lane >> 4;
-  const int logical0 = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_cls = (int)gridDim.x / g.ncls;  // merged parity classes (see ConvGeom)
-  const int cls = g.ncls > 1 ? logical0 / per_cls : 0;
-  const int logical = logical0 - cls * per_cls;
-  const int gK = g.cls_K[cls], gph = g.cls_ph[cls], gpw = g.cls_pw[cls], tap0 = g.cls_tap0[cls];
-  const uint16_t* eadd = (g.add_cls0_only && cls) ? nullptr : e.add;
-  const int tm = logical / tiles_n, tn = logical - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const TilePos tp = tile_place<BM, BN>(g, e, tiles_n);
+  const int m0 = tp.m0, n0 = tp.n0;
   const int wm = wave >> 1, wn = wave & 1;
   const bool phase = TRANSPOSED && g.ph >= 0;
 
   // A rows of this lane: piece j covers rows 8 (wave * PA + j) .. +7 -> row + lane / 8,
   // LDS chunk lane % 8 <- source chunk swz64(lane % 8, row)
-  int rbase[PA], rih[PA], riw[PA];
-  bool rok[PA];
+  RowG ra[PA];
 #pragma unroll
   for (int j = 0; j < PA; ++j) {
     const int row = 8 * (wave * PA + j) + (lane >> 3);
-    const Pix p = decode_pix(g, m0 + row);
-    int ih0, iw0;
-    if (!TRANSPOSED) {
-      ih0 = p.oh * g.stride - g.pad;
-      iw0 = p.ow * g.stride - g.pad;
-    } else if (phase) {
-      ih0 = p.oh;
-      iw0 = p.ow;
-    } else {  // stride-1 transposed gather: ih = oh + pad - kh
-      ih0 = p.oh + g.pad;
-      iw0 = p.ow + g.pad;
-    }
-    rih[j] = ih0;
-    riw[j] = iw0;
-    rok[j] = p.ok;
-    rbase[j] = ((p.n * g.SH + ih0) * g.SW + iw0) * g.SC + swz64(lane & 7, row) * 8;
+    ra[j] = row_gather<TRANSPOSED>(g, decode_pix(g, m0 + row), swz64(lane & 7, row) * 8);
   }
+  // Buffer-resource DMA: a padding piece gets an out-of-range offset and lands as zeros, and each
+  // piece's in-image test for every tap is one bit of a per-lane mask (tap_masks).
+  // (the B offsets are turned into bbyte only after the masks: computed here in one step, the
+  // forward instance needs four more VGPRs before the accumulators, profiles/r12_convparts)
   int boffs[PB];
   bool bok[PB];
 #pragma unroll
@@ -564,37 +641,9 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
     boffs[j] = col * g.wld + swz64(lane & 7, row) * 8;
   }
   const int cps_shift = g.c_shift - 6;  // log2(stages per tap)
-  // workgroup-uniform gather shift (dh, dw) of a tap
-  auto tap_shift = [&](int tap, int& dh, int& dw) {
-    if (phase) {
-      dh = g.dh[tap0 + tap];
-      dw = g.dw[tap0 + tap];
-    } else {
-      const int kh = (tap * g.kw_magic) >> 16, kw = tap - kh * g.KW;
-      dh = TRANSPOSED ? -kh : kh;
-      dw = TRANSPOSED ? -kw : kw;
-    }
-  };
-  // Buffer-resource DMA: a padding piece gets an out-of-range offset and lands as zeros, and
-  // each piece's in-image test for every tap is one bit of a per-lane mask computed here once,
-  // so a piece costs an add, a bit test and a select per stage (~10 VALU with 64-bit
-  // addresses and a zero-page select: profiles/r06_lean).  The host keeps both operands under 2 GB (plan_gemm).
-  const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.src), 0,
-                                                      (int)((long)g.N * g.SH * g.SW * g.SC * 2), 0x00020000);
-  const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(e.w), 0, (int)((long)e.ncols * g.wld * 2),
-                                                      0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
-  unsigned tmask[PA] = {};
-#pragma unroll 1
-  for (int tap = 0; tap < (gK / BK) >> cps_shift; ++tap) {
-    int dh, dw;
-    tap_shift(tap, dh, dw);
-#pragma unroll
-    for (int j = 0; j < PA; ++j) {
-      const bool v = rok[j] && (unsigned)(rih[j] + dh) < (unsigned)g.SH && (unsigned)(riw[j] + dw) < (unsigned)g.SW;
-      tmask[j] |= (unsigned)v << tap;
-    }
-  }
+  const ConvRsrc rs = conv_rsrc(g, e);
+  unsigned tmask[PA];
+  tap_masks<TRANSPOSED, BK>(g, tp, cps_shift, ra, tmask);
   unsigned bbyte[PB];
 #pragma unroll
   for (int j = 0; j < PB; ++j) bbyte[j] = bok[j] ? (unsigned)boffs[j] * 2u : OOB;  // + kb * 2 < 2 GB stays out
@@ -603,33 +652,27 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
     uint16_t* Bs = As + BM * BK;
     const int tap = kt >> cps_shift, ch0 = (kt & ((1 << cps_shift) - 1)) * 64;
     int dh, dw;
-    tap_shift(tap, dh, dw);
-    const int kb = phase ? g.tapw[tap0 + tap] * g.SC + ch0 : kt * BK;
+    tap_shift<TRANSPOSED>(g, tp.tap0, tap, dh, dw);
+    const int kb = phase ? g.tapw[tp.tap0 + tap] * g.SC + ch0 : kt * BK;
     const int soff = (dh * g.SW + dw) * g.SC + ch0;  // workgroup-uniform
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
-      const unsigned off = (tmask[j] >> tap) & 1u ? (unsigned)(rbase[j] + soff) * 2u : OOB;
-      blds16(rs_a, (SL_LDS void*)(As + (wave * PA + j) * 8 * BK), off);
+      const unsigned off = (tmask[j] >> tap) & 1u ? (unsigned)(ra[j].b32 + soff) * 2u : OOB;
+      blds16(rs.a, (SL_LDS void*)(As + (wave * PA + j) * 8 * BK), off);
     }
 #pragma unroll
     for (int j = 0; j < PB; ++j)
-      blds16(rs_b, (SL_LDS void*)(Bs + (wave * PB + j) * 8 * BK), bbyte[j] + (unsigned)kb * 2u);
+      blds16(rs.b, (SL_LDS void*)(Bs + (wave * PB + j) * 8 * BK), bbyte[j] + (unsigned)kb * 2u);
   };
 
   // Fragment i / j sits i * 16 rows past fragment 0 with the same swizzle (swz64 reads row bits
-  // 1-3): the reads use entry 0 per operand and 32-deep half, the rest as instruction offsets.
-  uint32_t aoff[MT][2], boff[NT][2];
+  // 1-3): one base per operand and 32-deep half, the rest as instruction offsets.
+  const int fa = wm * 64 + lr, fb = wn * 64 + lr;
+  uint32_t aoff[2], boff[2];
 #pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int r = wm * 64 + i * 16 + lr;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) aoff[i][h] = (uint32_t)((r * BK + swz64(h * 4 + lg, r) * 8) * 2);
-  }
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int r = wn * 64 + j * 16 + lr;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) boff[j][h] = (uint32_t)(((BM + r) * BK + swz64(h * 4 + lg, r) * 8) * 2);
+  for (int h = 0; h < 2; ++h) {
+    aoff[h] = (uint32_t)((fa * BK + swz64(h * 4 + lg, fa) * 8) * 2);
+    boff[h] = (uint32_t)(((BM + fb) * BK + swz64(h * 4 + lg, fb) * 8) * 2);
   }
   const uint32_t lds0 = (uint32_t)(uintptr_t)(SL_LDS const uint16_t*)smem;
 
@@ -639,7 +682,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = zero4();
 
-  const int nk = gK / BK;  // uniform taps: K is a multiple of 64
+  const int nk = tp.K / BK;  // uniform taps: K is a multiple of 64
   for (int kt = 0; kt < NSLOT - 1 && kt < nk; ++kt) issue(kt);
   for (int kt = 0; kt < nk; ++kt) {
     // this wave's pieces of stage kt have landed once only stage kt + 1's (if issued) remain
@@ -652,7 +695,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       static_assert(MT == 4 && NT == 4, "offset list");
-      const uint32_t a = sb + aoff[0][h], b = sb + boff[0][h];
+      const uint32_t a = sb + aoff[h], b = sb + boff[h];
       af[h][0] = ds_b128o<0>(a);
       af[h][1] = ds_b128o<16 * BK * 2>(a);
       af[h][2] = ds_b128o<32 * BK * 2>(a);
@@ -677,57 +720,12 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---- epilogue (as conv_gemm_kernel, 8 waves) ----
-  if (e.stats) {
-    float* rep = rsum_replica(e.stats, 2 * e.ncols);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      float s = 0.f, q = 0.f;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = acc[i][j][r];
-          s += v;
-          q += v * v;
-        }
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      const int col = n0 + wn * 64 + j * 16 + lr;
-      if (lg == 0 && col < e.ncols) {
-        rsum_add(rep, col, s);
-        rsum_add(rep, e.ncols + col, q);
-      }
-    }
-  }
-  if (e.yf) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int col = n0 + wn * 64 + j * 16 + lr;
-        if (col >= e.ncols) continue;
-        const float b = e.bias ? e.bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = m0 + wm * 64 + i * 16 + 4 * lg + r;
-          if (row < g.M) e.yf[(long)row * e.ncols + col] = acc[i][j][r] + b;
-        }
-      }
-  }
+  // ---- epilogue ----
+  if (e.stats) epi_stats(e, acc, n0 + wn * 64, lr, lg);
+  if (e.yf) epi_store_f32(e, g.M, acc, m0 + wm * 64, n0 + wn * 64, lr, lg);
   if (!e.y) return;
   uint16_t* Cs = smem;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int cl = wn * 64 + j * 16 + lr;
-      const float b = (e.bias && n0 + cl < e.ncols) ? e.bias[n0 + cl] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Cs[(wm * 64 + i * 16 + 4 * lg + r) * CS_LD + cl] = f2bf(acc[i][j][r] + b);
-    }
+  epi_stage<CS_LD>(e, acc, Cs, wm * 64, wn * 64, n0, lr, lg);
   // operand prefetch as in conv_gemm_kernel (ncols % 128 == 0: every chunk is whole)
   constexpr int CPR = BN / 8, EIT = BM * CPR / 512;
   const int cc = (tid % CPR) * 8, col = n0 + cc;
@@ -738,14 +736,9 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
 #pragma unroll
   for (int it = 0; it < EIT; ++it) {
     const int row = m0 + tid / CPR + it * (512 / CPR);
-    long orow = row;
-    if (phase) {
-      const Pix pq = decode_pix(g, row);
-      orow = ((long)pq.n * g.FH + 2 * pq.oh + gph) * g.FW + 2 * pq.ow + gpw;
-    }
     // rows past M load element 0 (unused): unconditional loads, cf. the stride-2 epilogue
-    eoff[it] = row < g.M ? orow * e.ldy + col : 0;
-    if (eadd) ea[it] = ld8(eadd + eoff[it]);
+    eoff[it] = row < g.M ? epi_chunk_off<TRANSPOSED>(g, e, tp, row, col) : 0;
+    if (tp.add) ea[it] = ld8(tp.add + eoff[it]);
     if (bnb) bnb_load(e.bn, eoff[it], ebn[it]);
   }
   BnbAcc bacc;
@@ -760,10 +753,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
   for (int it = 0; it < EIT; ++it) {
     const int rl = tid / CPR + it * (512 / CPR), row = m0 + rl;
     short8_t v = *reinterpret_cast<const short8_t*>(Cs + rl * CS_LD + cc);
-    if (eadd) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) v[t] = (short)f2bf(bf2f((uint16_t)v[t]) + bf2f((uint16_t)ea[it][t]));
-    }
+    if (tp.add) v = add_bf16x8(v, ea[it]);
     if (bnb && row < g.M) bnb_chunk(e.bn, ebn[it], v, msc, msh, bacc);
     vout[it] = v;
   }
@@ -793,7 +783,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(ConvGeom g, ConvE
 // >= 512 tiles (SL_GEMM_WIDE environment switch); at 256 tiles a CU would hold one 4-wave
 // workgroup.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int swz32(int c, int r) { return c ^ ((0x78 >> (2 * ((r >> 2) & 3))) & 3); }
 
 // BM = 128 (grids of 256 big tiles, ResNet-18 stage 4): 128 x 128 tiles, waves of 64 x 64, a
 // 48 KB ring (two workgroups per CU: three would spill the data gradient).
@@ -811,42 +800,19 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lg = lane >> 4;
-  const int logical0 = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_cls = (int)gridDim.x / g.ncls;
-  const int cls = g.ncls > 1 ? logical0 / per_cls : 0;
-  const int logical = logical0 - cls * per_cls;
-  const int gK = g.cls_K[cls], gph = g.cls_ph[cls], gpw = g.cls_pw[cls], tap0 = g.cls_tap0[cls];
-  const uint16_t* eadd = (g.add_cls0_only && cls) ? nullptr : e.add;
-  const int tm = logical / tiles_n, tn = logical - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const TilePos tp = tile_place<BM, BN>(g, e, tiles_n);
+  const int m0 = tp.m0, n0 = tp.n0;
   const int wm = wave >> 1, wn = wave & 1;
   const bool phase = TRANSPOSED && g.ph >= 0;
 
   // A rows of this lane: piece j covers rows 16 (wave * PA + j) .. +15 -> row + lane / 4,
   // LDS chunk lane % 4 <- source chunk swz32(lane % 4, row)
-  int rbase[PA], rih[PA], riw[PA];
-  bool rok[PA];
+  RowG ra[PA];
 #pragma unroll
   for (int j = 0; j < PA; ++j) {
     const int row = 16 * (wave * PA + j) + (lane >> 2);
-    const Pix p = decode_pix(g, m0 + row);
-    int ih0, iw0;
-    if (!TRANSPOSED) {
-      ih0 = p.oh * g.stride - g.pad;
-      iw0 = p.ow * g.stride - g.pad;
-    } else if (phase) {
-      ih0 = p.oh;
-      iw0 = p.ow;
-    } else {
-      ih0 = p.oh + g.pad;
-      iw0 = p.ow + g.pad;
-    }
-    rih[j] = ih0;
-    riw[j] = iw0;
-    rok[j] = p.ok;
-    rbase[j] = ((p.n * g.SH + ih0) * g.SW + iw0) * g.SC + swz32(lane & 3, row) * 8;
+    ra[j] = row_gather<TRANSPOSED>(g, decode_pix(g, m0 + row), swz32(lane & 3, row) * 8);
   }
-  constexpr unsigned OOB = 0x80000000u;
   unsigned bbyte[PB];
 #pragma unroll
   for (int j = 0; j < PB; ++j) {
@@ -855,54 +821,32 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
     bbyte[j] = col < e.ncols ? (unsigned)(col * g.wld + swz32(lane & 3, row) * 8) * 2u : OOB;
   }
   const int cps_shift = g.c_shift - 5;  // log2(stages per tap)
-  auto tap_shift = [&](int tap, int& dh, int& dw) {
-    if (phase) {
-      dh = g.dh[tap0 + tap];
-      dw = g.dw[tap0 + tap];
-    } else {
-      const int kh = (tap * g.kw_magic) >> 16, kw = tap - kh * g.KW;
-      dh = TRANSPOSED ? -kh : kh;
-      dw = TRANSPOSED ? -kw : kw;
-    }
-  };
-  const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.src), 0,
-                                                      (int)((long)g.N * g.SH * g.SW * g.SC * 2), 0x00020000);
-  const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(e.w), 0, (int)((long)e.ncols * g.wld * 2),
-                                                      0x00020000);
-  unsigned tmask[PA] = {};
-#pragma unroll 1
-  for (int tap = 0; tap < (gK / WBK) >> cps_shift; ++tap) {
-    int dh, dw;
-    tap_shift(tap, dh, dw);
-#pragma unroll
-    for (int j = 0; j < PA; ++j) {
-      const bool v = rok[j] && (unsigned)(rih[j] + dh) < (unsigned)g.SH && (unsigned)(riw[j] + dw) < (unsigned)g.SW;
-      tmask[j] |= (unsigned)v << tap;
-    }
-  }
+  const ConvRsrc rs = conv_rsrc(g, e);
+  unsigned tmask[PA];
+  tap_masks<TRANSPOSED, WBK>(g, tp, cps_shift, ra, tmask);
   auto issue = [&](int kt) {
     uint16_t* As = smem + (kt % NSLOT) * SLOT;
     uint16_t* Bs = As + BM * WBK;
     const int tap = kt >> cps_shift, ch0 = (kt & ((1 << cps_shift) - 1)) * WBK;
     int dh, dw;
-    tap_shift(tap, dh, dw);
-    const int kb = phase ? g.tapw[tap0 + tap] * g.SC + ch0 : kt * WBK;
+    tap_shift<TRANSPOSED>(g, tp.tap0, tap, dh, dw);
+    const int kb = phase ? g.tapw[tp.tap0 + tap] * g.SC + ch0 : kt * WBK;
     const int soff = (dh * g.SW + dw) * g.SC + ch0;
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
-      const unsigned off = (tmask[j] >> tap) & 1u ? (unsigned)(rbase[j] + soff) * 2u : OOB;
-      blds16(rs_a, (SL_LDS void*)(As + (wave * PA + j) * 16 * WBK), off);
+      const unsigned off = (tmask[j] >> tap) & 1u ? (unsigned)(ra[j].b32 + soff) * 2u : OOB;
+      blds16(rs.a, (SL_LDS void*)(As + (wave * PA + j) * 16 * WBK), off);
     }
 #pragma unroll
     for (int j = 0; j < PB; ++j)
-      blds16(rs_b, (SL_LDS void*)(Bs + (wave * PB + j) * 16 * WBK), bbyte[j] + (unsigned)kb * 2u);
+      blds16(rs.b, (SL_LDS void*)(Bs + (wave * PB + j) * 16 * WBK), bbyte[j] + (unsigned)kb * 2u);
   };
 
   // fragment i / j of a wave: row + 16 i, same swizzle (rows differ in bits >= 4): one base each
   const uint32_t lds0 = (uint32_t)(uintptr_t)(SL_LDS const uint16_t*)smem;
-  const int ra = wm * (BM / 2) + lr, rb = wn * 64 + lr;
-  const uint32_t aoff = (uint32_t)((ra * WBK + swz32(lg, ra) * 8) * 2);
-  const uint32_t boff = (uint32_t)(((BM + rb) * WBK + swz32(lg, rb) * 8) * 2);
+  const int fa = wm * (BM / 2) + lr, fb = wn * 64 + lr;
+  const uint32_t aoff = (uint32_t)((fa * WBK + swz32(lg, fa) * 8) * 2);
+  const uint32_t boff = (uint32_t)(((BM + fb) * WBK + swz32(lg, fb) * 8) * 2);
 
   floatx4_t acc[MT][NT];
 #pragma unroll
@@ -910,7 +854,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = zero4();
 
-  const int nk = gK / WBK;
+  const int nk = tp.K / WBK;
   for (int kt = 0; kt < NSLOT - 1 && kt < nk; ++kt) issue(kt);
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PS) : "memory");
@@ -949,46 +893,9 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---- epilogue (conv_gemm_big_kernel's, 4 waves; operands in two passes of 8 chunks) ----
-  if (e.stats) {
-    float* rep = rsum_replica(e.stats, 2 * e.ncols);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      float s = 0.f, q = 0.f;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = acc[i][j][r];
-          s += v;
-          q += v * v;
-        }
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      const int col = n0 + wn * 64 + j * 16 + lr;
-      if (lg == 0 && col < e.ncols) {
-        rsum_add(rep, col, s);
-        rsum_add(rep, e.ncols + col, q);
-      }
-    }
-  }
-  if (e.yf) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int col = n0 + wn * 64 + j * 16 + lr;
-        if (col >= e.ncols) continue;
-        const float bb = e.bias ? e.bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = m0 + wm * (BM / 2) + i * 16 + 4 * lg + r;
-          if (row < g.M) e.yf[(long)row * e.ncols + col] = acc[i][j][r] + bb;
-        }
-      }
-  }
+  // ---- epilogue (conv_gemm_big_kernel's pass structure, with the operands in two passes of 8 chunks) ----
+  if (e.stats) epi_stats(e, acc, n0 + wn * 64, lr, lg);
+  if (e.yf) epi_store_f32(e, g.M, acc, m0 + wm * (BM / 2), n0 + wn * 64, lr, lg);
   if (!e.y) return;
   constexpr int CPR = BN / 8, EIT = BM * CPR / NTHR, EP = 8;  // 16 (8) chunks per thread, 2 (1) passes
   const int cc = (tid % CPR) * 8, col = n0 + cc;
@@ -1004,27 +911,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
 #pragma unroll
     for (int it = 0; it < EP; ++it) {
       const int row = m0 + tid / CPR + (p0 + it) * (NTHR / CPR);
-      long orow = row;
-      if (phase) {
-        const Pix pq = decode_pix(g, row);
-        orow = ((long)pq.n * g.FH + 2 * pq.oh + gph) * g.FW + 2 * pq.ow + gpw;
-      }
-      in.off[it] = row < g.M ? orow * e.ldy + col : 0;
-      if (eadd) in.a[it] = ld8(eadd + in.off[it]);
+      in.off[it] = row < g.M ? epi_chunk_off<TRANSPOSED>(g, e, tp, row, col) : 0;
+      if (tp.add) in.a[it] = ld8(tp.add + in.off[it]);
       if (bnb) bnb_load(e.bn, in.off[it], in.bn[it]);
     }
   };
   EpiIn in0, in1;
   uint16_t* Cs = smem;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int cl = wn * 64 + j * 16 + lr;
-      const float bb = (e.bias && n0 + cl < e.ncols) ? e.bias[n0 + cl] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Cs[(wm * (BM / 2) + i * 16 + 4 * lg + r) * CS_LD + cl] = f2bf(acc[i][j][r] + bb);
-    }
+  epi_stage<CS_LD>(e, acc, Cs, wm * (BM / 2), wn * 64, n0, lr, lg);
   BnbAcc bacc;
   float msc[8], msh[8];
   if (bnb) bnb_init(e.bn, e.ncols, col, bacc, msc, msh);
@@ -1035,10 +929,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
     for (int it = 0; it < EP; ++it) {
       const int rl = tid / CPR + (p0 + it) * (NTHR / CPR), row = m0 + rl;
       short8_t v = *reinterpret_cast<const short8_t*>(Cs + rl * CS_LD + cc);
-      if (eadd) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = (short)f2bf(bf2f((uint16_t)v[t]) + bf2f((uint16_t)in.a[it][t]));
-      }
+      if (tp.add) v = add_bf16x8(v, in.a[it]);
       if (bnb && row < g.M) bnb_chunk(e.bn, in.bn[it], v, msc, msh, bacc);
       vout[it] = v;
     }
@@ -1098,7 +989,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wide_kernel(ConvGeom g, Conv
 // ---------------------------------------------------------------------------
 namespace {
 constexpr int S2_BK = 32;
-__device__ __forceinline__ int s2_swz(int c, int r) { return c ^ ((0x78 >> (2 * ((r >> 2) & 3))) & 3); }
 // pairs of window w: count, class (ph * 2 + pw), weight tap (kh * 3 + kw)
 __host__ __device__ constexpr int s2_npairs(int w) { return w == 0 ? 4 : w == 3 ? 1 : 2; }
 __host__ __device__ constexpr int s2_cls(int w, int q) {
@@ -1132,7 +1022,7 @@ __global__ __launch_bounds__(256, OCC) void conv_dgrad_s2_kernel(ConvGeom g, Con
   const int wm = wave >> 1, wn = wave & 1;
 
   // A rows of this lane: piece j covers rows 16 (wave * PA + j) .. +15 -> row + lane / 4,
-  // LDS chunk lane % 4 <- source chunk s2_swz(lane % 4, row)
+  // LDS chunk lane % 4 <- source chunk swz32(lane % 4, row)
   int abase[PA], ai[PA], aj[PA];
   bool aok[PA];
 #pragma unroll
@@ -1142,7 +1032,7 @@ __global__ __launch_bounds__(256, OCC) void conv_dgrad_s2_kernel(ConvGeom g, Con
     aok[j] = p.ok;
     ai[j] = p.oh;
     aj[j] = p.ow;
-    abase[j] = ((p.n * g.SH + p.oh) * g.SW + p.ow) * g.SC + s2_swz(lane & 3, row) * 8;
+    abase[j] = ((p.n * g.SH + p.oh) * g.SW + p.ow) * g.SC + swz32(lane & 3, row) * 8;
   }
   int bbase[PBQ];
   bool bok[PBQ];
@@ -1151,15 +1041,11 @@ __global__ __launch_bounds__(256, OCC) void conv_dgrad_s2_kernel(ConvGeom g, Con
     const int row = 16 * (wave * PBQ + j) + (lane >> 2);
     const int col = n0 + row;
     bok[j] = col < e.ncols;
-    bbase[j] = col * g.wld + s2_swz(lane & 3, row) * 8;
+    bbase[j] = col * g.wld + swz32(lane & 3, row) * 8;
   }
   // buffer-resource DMA (as conv_gemm_big_kernel; profiles/r06_s2lean): per window, the lane's source byte
   // offset at channel chunk 0, or an out-of-range offset (zeros) where the window leaves dY
-  const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.src), 0,
-                                                      (int)((long)g.N * g.SH * g.SW * g.SC * 2), 0x00020000);
-  const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(e.w), 0, (int)((long)e.ncols * g.wld * 2),
-                                                      0x00020000);
-  constexpr unsigned OOB = 0x80000000u;
+  const ConvRsrc rs = conv_rsrc(g, e);
   unsigned awin[4][PA], bbyte[PBQ];
 #pragma unroll
   for (int w = 0; w < 4; ++w)
@@ -1173,38 +1059,40 @@ __global__ __launch_bounds__(256, OCC) void conv_dgrad_s2_kernel(ConvGeom g, Con
   for (int j = 0; j < PBQ; ++j) bbyte[j] = bok[j] ? (unsigned)bbase[j] * 2u : OOB;
   // stage s = 4 * chunk + window.  The capture list is spelled out and names the row arrays
   // above although the body reads only awin / bbyte: hipcc's register allocation follows the
-  // closure's layout, and with a plain [&] the four instances come out with renumbered VGPRs.
-  // The list keeps the device code byte-identical to the measured one (profiles/r08_knobs);
-  // fold it into [&] with the next change that re-measures this kernel.
-  auto issue = [&wave, &rs_a, &awin, &g, &rs_b, &bbyte, &aok, &ai, &aj, &abase, &bok, &e, &bbase](
+  // closure's layout.  With a plain [&] and the arrays folded into the loops the instruction mix
+  // and the VGPR count stay, but the kernel measured 1.3 % slower (94.6 against 93.3 us,
+  // profiles/r12_convparts), so the parent's text stays.
+  auto issue = [&wave, &rs, &awin, &g, &bbyte, &aok, &ai, &aj, &abase, &bok, &e, &bbase](
                    int s, auto wc) __attribute__((always_inline)) {
     constexpr int W = decltype(wc)::value;
     uint16_t* As = smem + (s % NSLOT) * SLOT;
     const int ch0 = (s >> 2) * S2_BK;
 #pragma unroll
     for (int j = 0; j < PA; ++j)
-      blds16(rs_a, (SL_LDS void*)(As + (wave * PA + j) * 16 * S2_BK), awin[W][j] + (unsigned)ch0 * 2u);
+      blds16(rs.a, (SL_LDS void*)(As + (wave * PA + j) * 16 * S2_BK), awin[W][j] + (unsigned)ch0 * 2u);
 #pragma unroll
     for (int q = 0; q < s2_npairs(W); ++q) {
       uint16_t* Bs = As + A_EL + q * B_EL;
       const unsigned kb2 = (unsigned)(s2_tap(W, q) * g.SC + ch0) * 2u;
 #pragma unroll
-      for (int j = 0; j < PBQ; ++j) blds16(rs_b, (SL_LDS void*)(Bs + (wave * PBQ + j) * 16 * S2_BK), bbyte[j] + kb2);
+      for (int j = 0; j < PBQ; ++j) blds16(rs.b, (SL_LDS void*)(Bs + (wave * PBQ + j) * 16 * S2_BK), bbyte[j] + kb2);
     }
   };
 
-  // Fragment i / j sits i * 16 rows past fragment 0 with the same swizzle (s2_swz reads row bits
-  // 2-3): the reads use entry 0 per operand, the rest as instruction offsets.
+  // Fragment i / j sits i * 16 rows past fragment 0 with the same swizzle (swz32 reads row bits
+  // 2-3): the reads use entry 0 per operand, the rest as instruction offsets.  The unused entries
+  // stay: with one base per operand two of the four instances need more VGPRs
+  // (profiles/r12_convparts).
   uint32_t aoff[MT], boff[NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const int r = wm * (BM / 2) + i * 16 + lr;
-    aoff[i] = (uint32_t)((r * S2_BK + s2_swz(lg, r) * 8) * 2);
+    aoff[i] = (uint32_t)((r * S2_BK + swz32(lg, r) * 8) * 2);
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int r = wn * (BN / 2) + j * 16 + lr;
-    boff[j] = (uint32_t)((r * S2_BK + s2_swz(lg, r) * 8) * 2);
+    boff[j] = (uint32_t)((r * S2_BK + swz32(lg, r) * 8) * 2);
   }
   const uint32_t lds0 = (uint32_t)(uintptr_t)(SL_LDS const uint16_t*)smem;
 
@@ -1286,7 +1174,10 @@ __global__ __launch_bounds__(256, OCC) void conv_dgrad_s2_kernel(ConvGeom g, Con
     short8_t ea[EIT];
     BnbIn ebn[EIT];
     // this class's residual / BN operands, issued before the barrier and the LDS staging so
-    // their latency hides under both (profiles/r05_s2epi)
+    // their latency hides under both (profiles/r05_s2epi).  An immediately-called lambda with the
+    // offset spelled out (epi_chunk_off's phase form): as a plain loop hipcc decodes the pixel
+    // again for every class (+130 VALU), and with epi_chunk_off the VGPR count changes
+    // (profiles/r12_convparts).
     auto epi_loads = [&]() __attribute__((always_inline)) {
 #pragma unroll
       for (int it = 0; it < EIT; ++it) {
@@ -1321,10 +1212,7 @@ __global__ __launch_bounds__(256, OCC) void conv_dgrad_s2_kernel(ConvGeom g, Con
       if (row >= g.M || !full) continue;  // the host guarantees ncols % 8 == 0
       short8_t v = *reinterpret_cast<const short8_t*>(Cs + rl * CS_LD + cc);
       if ((rl >> 3) & 1) v = __builtin_shufflevector(v, v, 4, 5, 6, 7, 0, 1, 2, 3);
-      if (eadd) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = (short)f2bf(bf2f((uint16_t)v[t]) + bf2f((uint16_t)ea[it][t]));
-      }
+      if (eadd) v = add_bf16x8(v, ea[it]);
       if (bnb) bnb_chunk(e.bn, ebn[it], v, msc, msh, bacc);
       *reinterpret_cast<short8_t*>(e.y + eoff[it]) = v;
     }
@@ -1516,11 +1404,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a) {
   const int t = logical - s * tiles;
   const int tco = t / a.tiles_k, tk = t - tco * a.tiles_k;
   const int co0 = tco * BMO, k0 = tk * BNO;
-  // wave is 0..3 (256 threads), which hipcc does not derive: the mask here and the guard on the
-  // epilogue's LDS stores are no-ops that the measured device code contains; they stay so that
-  // it is byte-identical (profiles/r08_knobs) and go with the next change that re-measures it
-  const int w4 = wave & 3;
-  const int wm = w4 >> 1, wn = w4 & 1;
+  const int wm = wave >> 1, wn = wave & 1;
   const int mbeg = s * a.steps_per_slice * WGM;
   const int nst = min(a.steps_per_slice, (g.M - mbeg + WGM - 1) / WGM);
 
@@ -1653,15 +1537,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a) {
 
   // fp32 tile through LDS so each wave's atomics cover 256 contiguous bytes
   float* Os = reinterpret_cast<float*>(smem);
-  if ((wave >> 2) == 0) {  // always (see w4)
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
+  for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int j = 0; j < NT; ++j)
+    for (int j = 0; j < NT; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          Os[(wm * (BMO / 2) + i * 16 + 4 * lg + r) * OUT_LD + wn * (BNO / 2) + j * 16 + lr] = acc[i][j][r];
-  }
+      for (int r = 0; r < 4; ++r)
+        Os[(wm * (BMO / 2) + i * 16 + 4 * lg + r) * OUT_LD + wn * (BNO / 2) + j * 16 + lr] = acc[i][j][r];
   __syncthreads();
   static_assert(BNO == 128, "wgrad_store_tile writes 128-column tiles");
   wgrad_store_tile<BMO, OUT_LD, 256>(a, s, co0, k0, Os, tid);
