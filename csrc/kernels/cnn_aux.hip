@@ -7,6 +7,8 @@
 //
 //   input_norm      u8 [N][H][W][3] -> bf16 [N][H][W][8] ((x/255 - mean_c)/std_c, pad channels 0),
 //                   batch chosen by a device cursor (hipGraph replay)
+//   input_aug       the same, with the records drawn through a per-epoch permutation and/or a random
+//                   crop (zero padding) + horizontal flip, all a pure function of (seed, cursor, sample)
 //   bn_finalize     conv-epilogue sums -> scale/shift/mean/rstd, running-stat update
 //   bn_apply        y = relu?(x*scale + shift + r), r = 0 | res | res*rscale + rshift
 //   bn_bwd_reduce   dz = dy*1[y>0]; per-channel sum(dz), sum(dz*x) (+ dz out for the skip)
@@ -15,6 +17,7 @@
 //   maxpool / avgpool fwd+bwd, softmax cross-entropy (loss, correct, dlogits, dbias)
 #include "common.h"
 #include "bn_fwd.h"
+#include "philox.h"
 
 using namespace sl;
 
@@ -36,21 +39,117 @@ static int blocks_for(long items, int cap = 4096) {
 }
 
 // ---------------------------------------------------------------------------
+// (a*v + b per channel) of a pixel's three u8 values: a = 1/(255 std_c), b = -mean_c/std_c
+struct NormCoef {
+  float a0, a1, a2, b0, b1, b2;
+};
+
+// One pixel's three u8 channels -> 8 bf16 (channels 3-7 zero).  The one copy of the arithmetic:
+// input_norm and input_aug give the same u8 values the same bits.
+__device__ __forceinline__ short8_t norm_pack8(uint8_t r, uint8_t g, uint8_t b, const NormCoef& c) {
+  float f[8] = {r * c.a0 + c.b0, g * c.a1 + c.b1, b * c.a2 + c.b2, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return pack8(f);
+}
+
 // Batch `cursor % n_batches` of a device-resident u8 shard -> normalised bf16
 // (and its labels), so a captured step replays on fresh data with no host work.
 __global__ __launch_bounds__(256) void input_norm_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ lab,
                                                          const int* __restrict__ cursor, int n_batches, int batch,
                                                          long img_pixels, uint16_t* __restrict__ y,
-                                                         uint8_t* __restrict__ lab_out, float a0, float a1, float a2,
-                                                         float b0, float b1, float b2) {
+                                                         uint8_t* __restrict__ lab_out, NormCoef c) {
   const long b = cursor ? (long)(*cursor % n_batches) : 0;
   const long pixels = (long)batch * img_pixels;
   const uint8_t* src = x + b * pixels * 3;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += (long)gridDim.x * blockDim.x) {
     const uint8_t* s = src + p * 3;
-    float f[8] = {s[0] * a0 + b0, s[1] * a1 + b1, s[2] * a2 + b2, 0.f, 0.f, 0.f, 0.f, 0.f};
-    *reinterpret_cast<short8_t*>(y + p * 8) = pack8(f);
+    *reinterpret_cast<short8_t*>(y + p * 8) = norm_pack8(s[0], s[1], s[2], c);
     if (lab_out && p < batch) lab_out[p] = lab[b * batch + p];
+  }
+}
+
+// Pixels per thread of input_aug_kernel (256 apart, so a wave's accesses stay contiguous).  The
+// per-image prologue is ~450 scalar instructions in every wave; at one pixel per thread it bound the
+// kernel with both parts on (12.9-13.0 us at B = 1024, 32x32, against 10.7-11.0 us at 2, 4 or 8
+// in the same run: profiles/r13_input).
+constexpr int AUG_PX = 4;
+
+// murmur3 finalizer: the round function of the shuffle's Feistel network
+__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x;
+}
+
+// Input pipeline of a training step (serverless_learn_amd/data/augment.py is the definition):
+// sample j of the batch at cursor t takes record perm_e(b*B + j) of the shard (e = t / nb,
+// b = t % nb; a 4-round Feistel bijection of [0, 2^(2h)) keyed by Philox(e; stream 1), cycle-walked
+// into [0, N)), shifted by (oy - pad, ox - pad) with black padding and mirrored when flip
+// (Philox(t, j; stream 2)).  blockIdx.y is the sample, so everything up to the record's base
+// pointer depends on kernel arguments, blockIdx and the cursor alone: it is computed once per
+// workgroup, in scalar registers.  A thread then does what input_norm's does, for up to AUG_PX
+// pixels of the image: three byte loads (none for padding), one 16-B store.
+// flags: 1 = shuffle, 2 = crop + flip.
+__global__ __launch_bounds__(256) void input_aug_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ lab,
+                                                        const int* __restrict__ cursor, uint32_t n_records,
+                                                        uint32_t batch, int H, int W, int pad, int flags, int half_bits,
+                                                        uint32_t k0, uint32_t k1, uint16_t* __restrict__ y,
+                                                        uint8_t* __restrict__ lab_out, int* __restrict__ params_out,
+                                                        NormCoef c) {
+  const uint32_t j = blockIdx.y;
+  const uint32_t t = (uint32_t)*cursor;  // a non-negative int32
+  const uint32_t nb = n_records / batch;
+  const uint32_t e = t / nb, b = t - e * nb;
+  uint32_t rec = b * batch + j;  // < nb * batch <= n_records
+  if (flags & 1) {
+    const U4 key = philox4x32_10(e, 0u, 0u, 1u, k0, k1);
+    const uint32_t kk[4] = {key.x, key.y, key.z, key.w};
+    const uint32_t mask = (1u << half_bits) - 1u;
+    // a bijection of [0, 2^(2h)) iterated from a value below n_records comes back below it: the
+    // walk ends, and rec < n_records keeps every load inside the shard
+    do {
+      uint32_t L = rec >> half_bits, R = rec & mask;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t nr = L ^ (fmix32(R + kk[i]) & mask);
+        L = R;
+        R = nr;
+      }
+      rec = (L << half_bits) | R;
+    } while (rec >= n_records);
+  }
+  int oy = pad, ox = pad, flip = 0;
+  if (flags & 2) {
+    const U4 r = philox4x32_10(t, 0u, j, 2u, k0, k1);
+    const uint32_t span = 2u * (uint32_t)pad + 1u;
+    oy = (int)(r.x % span);
+    ox = (int)(r.y % span);
+    flip = (int)(r.z & 1u);
+  }
+  const int p0 = blockIdx.x * (256 * AUG_PX) + threadIdx.x;
+  if (p0 == 0) {
+    if (params_out) *reinterpret_cast<int4*>(params_out + 4 * j) = make_int4((int)rec, oy, ox, flip);
+    if (lab_out) lab_out[j] = lab[rec];
+  }
+  const int img = H * W;
+  const uint8_t* src = x + (long)rec * img * 3;
+  uint16_t* dst = y + (long)j * img * 8;
+#pragma unroll
+  for (int k = 0; k < AUG_PX; ++k) {
+    const int p = p0 + k * 256;
+    if (p >= img) break;
+    const int py = p / W, px = p - py * W;
+    const int sy = py + oy - pad, sx = (flip ? W - 1 - px : px) + ox - pad;
+    uint8_t v0 = 0, v1 = 0, v2 = 0;  // outside the image: black before normalisation
+    if ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) {
+      const uint8_t* s = src + ((long)sy * W + sx) * 3;
+      v0 = s[0];
+      v1 = s[1];
+      v2 = s[2];
+    }
+    *reinterpret_cast<short8_t*>(dst + (long)p * 8) = norm_pack8(v0, v1, v2, c);
   }
 }
 
@@ -596,6 +695,10 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
 extern "C" int sl_rsum_fold(float* buf, int n, hipStream_t stream);  // conv.hip
 extern "C" int sl_rsum_fold2(float* buf, float* buf2, int n, hipStream_t stream);  // conv.hip
 
+static NormCoef norm_coef(float m0, float m1, float m2, float s0, float s1, float s2) {
+  return NormCoef{1.f / (255.f * s0), 1.f / (255.f * s1), 1.f / (255.f * s2), -m0 / s0, -m1 / s1, -m2 / s2};
+}
+
 extern "C" {
 
 long sl_rsum_floats(int n) { return rsum_floats(n); }
@@ -605,15 +708,30 @@ int sl_deterministic() { return SL_DETERMINISTIC; }
 int sl_input_norm(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_batches, int batch,
                   long img_pixels, uint16_t* y, uint8_t* lab_out, float m0, float m1, float m2, float s0, float s1,
                   float s2, hipStream_t stream) {
-  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
-  float a[3], b[3];
-  for (int i = 0; i < 3; ++i) {
-    a[i] = 1.f / (255.f * stdv[i]);
-    b[i] = -mean[i] / stdv[i];
-  }
   if (n_batches < 1 || batch < 1) return -1;
   hipLaunchKernelGGL(input_norm_kernel, dim3(blocks_for((long)batch * img_pixels)), dim3(256), 0, stream, x, lab,
-                     cursor, n_batches, batch, img_pixels, y, lab_out, a[0], a[1], a[2], b[0], b[1], b[2]);
+                     cursor, n_batches, batch, img_pixels, y, lab_out, norm_coef(m0, m1, m2, s0, s1, s2));
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// flags: 1 = epoch shuffle, 2 = random crop (zero padding `pad`) + horizontal flip.  The grid is
+// (pixel tiles, batch): a function of (batch, H, W) alone, so a captured graph replays it.
+int sl_input_aug(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_records, int batch, int H, int W,
+                 int pad, int flags, unsigned long long seed, uint16_t* y, uint8_t* lab_out, int* params_out, float m0,
+                 float m1, float m2, float s0, float s1, float s2, hipStream_t stream) {
+  if (!x || !cursor || !y || (lab_out && !lab)) return -2;
+  if (batch < 1 || batch > 65535 || n_records < batch || H < 1 || W < 1 || (long)H * W > (1L << 30)) return -1;
+  if (pad < 0 || pad >= H || pad >= W || (flags & ~3)) return -1;
+  // the Feistel network's half width: an even number of bits that holds n_records - 1
+  int bits = 0;
+  while (bits < 32 && ((unsigned long long)(n_records - 1) >> bits)) ++bits;
+  if (bits < 2) bits = 2;
+  const int half_bits = (bits + 1) / 2;
+  hipLaunchKernelGGL(input_aug_kernel, dim3((H * W + 256 * AUG_PX - 1) / (256 * AUG_PX), batch), dim3(256), 0,
+                     stream, x, lab, cursor,
+                     (uint32_t)n_records, (uint32_t)batch, H, W, pad, flags, half_bits, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), y, lab_out, params_out, norm_coef(m0, m1, m2, s0, s1, s2));
   SL_CHECK_LAUNCH();
   return 0;
 }

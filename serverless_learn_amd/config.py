@@ -68,6 +68,9 @@ class Config:
     lr_decay_steps: int = 0            # step at which the decay ends (0 = max_steps)
     lr_min_ratio: float = 0.0          # the decay ends at lr_min_ratio * lr
     clip_grad_norm: float = 0.0        # clip the aggregated gradient to this global L2 norm (0 = off, inf = measure)
+    augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip, data/augment.py)
+    augment_pad: int = 4               # crop-flip: black pixels of padding around the image the crop is taken from
+    shuffle: bool = False              # resnet18: draw each epoch's records through a fresh permutation of the shard
     seed: int = 0
     checkpoint_every: int = 0          # steps between checkpoints (rank 0); 0 = off
     max_steps: int = 0                 # 0 = run until stopped
@@ -96,7 +99,11 @@ class Config:
         self.validate()
 
     def validate(self) -> None:
-        """Refuse combinations no component implements (so far: the top-k sparse gossip's)."""
+        """Refuse combinations no component implements (the input pipeline's and the top-k sparse
+        gossip's)."""
+        if (self.augment, self.augment_pad, self.shuffle) != ("none", 4, False) and self.model in ("mlp", "simulate"):
+            # the MLP kernels read X from bricks tiled once per shard: a per-sample gather would undo that
+            raise ValueError(f"augment / shuffle: the {self.model} model has no input pipeline (model='resnet18')")
         x = self.gossip_topk
         if x == 0:
             return

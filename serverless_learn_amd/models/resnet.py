@@ -250,10 +250,17 @@ class CPUResNetTrainer(OptStateCPU):
 
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 5e-4,
                  seed: int = 0, world_size: int = 1, stem: str = "cifar", flat: torch.Tensor | None = None,
-                 in_hw: int | None = None, **opt):
+                 in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
+                 **opt):
+        from ..data import augment as A
         from .mlp import StepStats, sgd_update  # noqa: F401
 
         self.spec = resnet18_spec(stem, 10, in_hw)
+        A.check(augment, augment_pad, self.spec.in_hw)
+        # the training input pipeline (data/augment.py), keyed on (seed, cursor, sample) like the
+        # GPU engine's; last_aug is the last batch's (record, oy, ox, flip), None with it off
+        self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
+        self.last_aug = None
         self.batch = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
@@ -292,9 +299,17 @@ class CPUResNetTrainer(OptStateCPU):
         self.n_batches = self.x.shape[0] // self.batch
 
     def step(self) -> None:
-        b = self.cursor % self.n_batches
-        xs = self.x[b * self.batch:(b + 1) * self.batch]
-        ys = self.y[b * self.batch:(b + 1) * self.batch]
+        if self.shuffle or self.augment != "none":
+            from ..data import augment as A
+
+            self.last_aug = A.batch_params(self.seed, self.cursor, self.x.shape[0], self.batch, self.augment_pad,
+                                           self.shuffle, self.augment)
+            xs = torch.from_numpy(A.apply(self.x.cpu().numpy(), self.last_aug, self.augment_pad))
+            ys = self.y[torch.from_numpy(self.last_aug[:, 0].astype(np.int64))]
+        else:
+            b = self.cursor % self.n_batches
+            xs = self.x[b * self.batch:(b + 1) * self.batch]
+            ys = self.y[b * self.batch:(b + 1) * self.batch]
         loss, correct, g = ref_grads(self.spec, self.params, xs, ys, 1.0 / (self.batch * self.world_size),
                                      self.running)
         self.phases.mark("compute")

@@ -8,7 +8,8 @@ and replayed with zero host work (the data batch is chosen by a device-side
 cursor, like the MLP engine).
 
 Per step:
-  forward   input_norm -> [conv (+BN stats in the epilogue) -> bn_apply with
+  forward   input_norm (input_aug with shuffle= / augment= on: data/augment.py) ->
+            [conv (+BN stats in the epilogue) -> bn_apply with
             the finalize folded in (+residual, ReLU)] x 20 -> avgpool -> fc ->
             softmax-CE (loss, dlogits, dbias); a 64-channel block's conv2 applies
             relu(bn1(.)) while loading c1 instead (BN-on-load, no a1 pass)
@@ -78,14 +79,20 @@ class FusedResNetTrainer(GraphSlots):
     def __init__(self, batch: int, device="cuda", lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 5e-4, seed: int = 0, world_size: int = 1, stem: str = "cifar",
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
-                 in_hw: int | None = None, **opt):
+                 in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
+                 **opt):
+        from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
         from ..ops import optim as O
 
+        self.spec = spec = resnet18_spec(stem, classes, in_hw)
+        A.check(augment, augment_pad, spec.in_hw)
         _native.lib()
         self.K, self.O = K, O
-        self.spec = spec = resnet18_spec(stem, classes, in_hw)
+        # the training input pipeline (data/augment.py): a pure function of (seed, cursor, sample),
+        # so the cursor that is checkpointed and broadcast already is all the state it has
+        self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
         dev = self.device = torch.device(device)
         self.batch = B = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
@@ -138,6 +145,10 @@ class FusedResNetTrainer(GraphSlots):
         hw = spec.in_hw
         self.x0 = torch.empty(B, hw, hw, 8, **bf)
         self.labels = torch.zeros(B, dtype=torch.uint8, device=dev)
+        # (record, oy, ox, flip) of every sample of the last training batch, written by input_aug;
+        # None with the pipeline off (input_norm feeds the network, as in every evaluation path)
+        self.aug_out = (torch.zeros(B, 4, dtype=torch.int32, device=dev)
+                        if self.shuffle or augment != "none" else None)
         # ---- stem buffers ----
         sc = spec.stem_conv
         s_hw = K.out_size(hw, sc.k, sc.stride, sc.pad)
@@ -246,6 +257,8 @@ class FusedResNetTrainer(GraphSlots):
         self.wt()
 
     def load_shard(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> None:
+        """The resident shard.  With the input pipeline on, the epoch is cursor // (N // batch): a
+        shard of another size changes N // batch from the next step on, so the epoch index jumps."""
         hw = self.spec.in_hw
         x = x_u8.reshape(-1, hw, hw, 3)
         if x.shape[0] < self.batch:
@@ -263,7 +276,12 @@ class FusedResNetTrainer(GraphSlots):
     def forward(self, train: bool = True):
         K, spec = self.K, self.spec
         self.arena.zero_()
-        K.input_norm(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)
+        if train and self.aug_out is not None:
+            K.input_aug(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, self.aug_out, CIFAR_MEAN,
+                        CIFAR_STD, seed=self.seed, shuffle=self.shuffle, augment=self.augment,
+                        pad=self.augment_pad)
+        else:
+            K.input_norm(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)
         sbn = self.bn[spec.stem_bn.name]
         self._conv_bn(self.x0, self.conv["stem"], sbn, self.c0)
         cnt0 = self.c0.numel() // 64

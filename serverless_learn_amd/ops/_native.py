@@ -21,6 +21,7 @@ from ..build import KERNELS_DET_SO, KERNELS_SO
 
 _lock = threading.Lock()
 _lib = None
+_lib_is_default = True  # False: an A/B build loaded through SL_KERNELS_SO, which may lack newer kernels
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -62,7 +63,7 @@ def register(name: str, argtypes: list, restype=ctypes.c_int) -> None:
     _SIGS[name] = argtypes
     if restype is not ctypes.c_int:
         _RESTYPE[name] = restype
-    if _lib is not None:
+    if _lib is not None and (_lib_is_default or hasattr(_lib, name)):  # (an A/B build: as in lib())
         _bind(_lib, name)
 
 
@@ -78,7 +79,7 @@ def available() -> bool:
 
 def lib():
     """Load (building first if needed) the kernel library."""
-    global _lib
+    global _lib, _lib_is_default
     if _lib is not None:
         return _lib
     with _lock:
@@ -90,8 +91,9 @@ def lib():
 
                 build_kernels(deterministic=det)
             handle = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+            _lib_is_default = path in (KERNELS_SO, KERNELS_DET_SO)
             for name in _SIGS:
-                if path not in (KERNELS_SO, KERNELS_DET_SO) and not hasattr(handle, name):
+                if not _lib_is_default and not hasattr(handle, name):
                     continue  # an A/B build of older kernels: only what it exports
                 _bind(handle, name)
             _lib = handle

@@ -26,6 +26,7 @@ N.register("sl_conv_wgrad_ws_need", [], ctypes.c_long)
 N.register("sl_conv_wt", [P, I, L, P])
 N.register("sl_conv_wt_desc_size", [])
 N.register("sl_input_norm", [P, P, P, I, I, L, P, P, F, F, F, F, F, F, P])
+N.register("sl_input_aug", [P, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P, P, F, F, F, F, F, F, P])
 N.register("sl_cursor_bump", [P, P])
 N.register("sl_bn_finalize", [P, P, P, P, P, P, I, F, F, F, P])
 N.register("sl_bn_apply", [P, P, P, P, P, L, I, I, I, P])
@@ -322,6 +323,27 @@ def input_norm(x_u8, labels, cursor, batch: int, y, lab_out, mean, std):
     assert n_batches >= 1 and y.shape[0] == batch
     N.call("sl_input_norm", p(x_u8), p(labels), p(cursor), n_batches, batch, img, _bf16(y), p(lab_out),
            *[float(v) for v in mean], *[float(v) for v in std], N.stream_ptr())
+
+
+def input_aug(x_u8, labels, cursor, batch: int, y, lab_out, params_out, mean, std, seed: int = 0,
+              shuffle: bool = False, augment: str = "none", pad: int = 4):
+    """The training input pipeline (data/augment.py): sample j of the batch at ``cursor`` is a record
+    of the shard x_u8 [n,H,W,3] -- drawn through the epoch's permutation with ``shuffle`` -- cropped at
+    a random offset out of its zero-padded image and mirrored at random with ``augment="crop-flip"``,
+    then normalised as :func:`input_norm` does -> y [batch,H,W,8] bf16 (+ labels).  ``params_out``
+    (int32 [batch, 4]) receives each sample's (record, oy, ox, flip)."""
+    from ..data import augment as A
+
+    assert x_u8.dtype == torch.uint8 and x_u8.shape[-1] == 3 and y.shape[-1] == 8 and x_u8.is_contiguous()
+    n, h, w = x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]
+    A.check(augment, pad, min(h, w))
+    assert n >= batch and y.shape[0] == batch and tuple(y.shape[1:3]) == (h, w)
+    assert labels.dtype == torch.uint8 and labels.numel() >= n and lab_out.numel() >= batch
+    assert params_out.dtype == torch.int32 and params_out.numel() == 4 * batch and params_out.is_contiguous()
+    assert cursor.dtype == torch.int32
+    N.call("sl_input_aug", p(x_u8), p(labels), p(cursor), n, batch, h, w, pad, A.flags(shuffle, augment),
+           seed & ((1 << 64) - 1), _bf16(y), p(lab_out), p(params_out), *[float(v) for v in mean],
+           *[float(v) for v in std], N.stream_ptr())
 
 
 def cursor_bump(cursor):

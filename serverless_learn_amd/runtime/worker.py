@@ -153,6 +153,9 @@ class Worker:
                       lr_decay_steps=c.lr_decay_steps or c.max_steps, lr_min_ratio=c.lr_min_ratio)
         if c.clip_grad_norm != 0:  # under any rule (a negative value or NaN is refused by OptSpec)
             kw.update(clip_grad_norm=c.clip_grad_norm)
+        if (c.augment, c.augment_pad, c.shuffle) != ("none", 4, False):
+            # (an unknown name or a bad pad is refused by the trainer, data/augment.py check)
+            kw.update(augment=c.augment, augment_pad=c.augment_pad, shuffle=c.shuffle)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
