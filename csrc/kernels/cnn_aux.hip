@@ -9,15 +9,19 @@
 //                   batch chosen by a device cursor (hipGraph replay)
 //   input_aug       the same, with the records drawn through a per-epoch permutation and/or a random
 //                   crop (zero padding) + horizontal flip, all a pure function of (seed, cursor, sample)
+//   input_mix       input_aug, then mixup or CutMix with another sample of the batch (integer blend)
 //   bn_finalize     conv-epilogue sums -> scale/shift/mean/rstd, running-stat update
 //   bn_apply        y = relu?(x*scale + shift + r), r = 0 | res | res*rscale + rshift
 //   bn_bwd_reduce   dz = dy*1[y>0]; per-channel sum(dz), sum(dz*x) (+ dz out for the skip)
 //   bn_bwd_finalize -> dgamma, dbeta (into the flat gradient) and dx = a*dz + b*x + c coefficients
 //   bn_bwd_apply    dx = a*dz + b*x + c
-//   maxpool / avgpool fwd+bwd, softmax cross-entropy (loss, correct, dlogits, dbias)
+//   maxpool / avgpool fwd+bwd, softmax cross-entropy (loss, correct, dlogits, dbias), against
+//                   one-hot labels or soft targets (label smoothing, the label pair of a mixed sample)
 #include "common.h"
 #include "bn_fwd.h"
 #include "philox.h"
+
+#include <tuple>
 
 using namespace sl;
 
@@ -44,11 +48,20 @@ struct NormCoef {
   float a0, a1, a2, b0, b1, b2;
 };
 
-// One pixel's three u8 channels -> 8 bf16 (channels 3-7 zero).  The one copy of the arithmetic:
-// input_norm and input_aug give the same u8 values the same bits.
-__device__ __forceinline__ short8_t norm_pack8(uint8_t r, uint8_t g, uint8_t b, const NormCoef& c) {
+// One pixel's three channels, in pixel units (0..255, fractions allowed) -> 8 bf16 (channels 3-7
+// zero).  The one copy of the arithmetic: input_norm, input_aug and input_mix give the same values
+// the same bits.  Each channel is one fused multiply-add (v_fma_f32 / v_pk_fma_f32 in all three
+// kernels): the contraction of `v * a + b` is asked for here and not left to the build's default,
+// so a reference knows what to emulate -- round(v * a + b) once to fp32.  (fmaf() gives the same
+// instructions in another register allocation, which would move input_norm_kernel's code.)
+__device__ __forceinline__ short8_t norm_pack8(float r, float g, float b, const NormCoef& c) {
+#pragma clang fp contract(fast)
   float f[8] = {r * c.a0 + c.b0, g * c.a1 + c.b1, b * c.a2 + c.b2, 0.f, 0.f, 0.f, 0.f, 0.f};
   return pack8(f);
+}
+
+__device__ __forceinline__ short8_t norm_pack8(uint8_t r, uint8_t g, uint8_t b, const NormCoef& c) {
+  return norm_pack8((float)(int)r, (float)(int)g, (float)(int)b, c);
 }
 
 // Batch `cursor % n_batches` of a device-resident u8 shard -> normalised bf16
@@ -83,23 +96,19 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {
   return x;
 }
 
-// Input pipeline of a training step (serverless_learn_amd/data/augment.py is the definition):
-// sample j of the batch at cursor t takes record perm_e(b*B + j) of the shard (e = t / nb,
-// b = t % nb; a 4-round Feistel bijection of [0, 2^(2h)) keyed by Philox(e; stream 1), cycle-walked
-// into [0, N)), shifted by (oy - pad, ox - pad) with black padding and mirrored when flip
-// (Philox(t, j; stream 2)).  blockIdx.y is the sample, so everything up to the record's base
-// pointer depends on kernel arguments, blockIdx and the cursor alone: it is computed once per
-// workgroup, in scalar registers.  A thread then does what input_norm's does, for up to AUG_PX
-// pixels of the image: three byte loads (none for padding), one 16-B store.
+// (record, oy, ox, flip) of sample j of the batch at cursor t (serverless_learn_amd/data/augment.py
+// is the definition): record perm_e(b*B + j) of the shard (e = t / nb, b = t % nb; a 4-round Feistel
+// bijection of [0, 2^(2h)) keyed by Philox(e; stream 1), cycle-walked into [0, N)), offsets and flip
+// from Philox(t, j; stream 2).  Everything depends on kernel arguments, j and the cursor alone: with
+// j uniform in a workgroup it is computed once per workgroup, in scalar registers.
 // flags: 1 = shuffle, 2 = crop + flip.
-__global__ __launch_bounds__(256) void input_aug_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ lab,
-                                                        const int* __restrict__ cursor, uint32_t n_records,
-                                                        uint32_t batch, int H, int W, int pad, int flags, int half_bits,
-                                                        uint32_t k0, uint32_t k1, uint16_t* __restrict__ y,
-                                                        uint8_t* __restrict__ lab_out, int* __restrict__ params_out,
-                                                        NormCoef c) {
-  const uint32_t j = blockIdx.y;
-  const uint32_t t = (uint32_t)*cursor;  // a non-negative int32
+struct AugDraw {
+  uint32_t rec;
+  int oy, ox, flip;
+};
+
+__device__ __forceinline__ AugDraw aug_draw(uint32_t j, uint32_t t, uint32_t n_records, uint32_t batch, int pad,
+                                            int flags, int half_bits, uint32_t k0, uint32_t k1) {
   const uint32_t nb = n_records / batch;
   const uint32_t e = t / nb, b = t - e * nb;
   uint32_t rec = b * batch + j;  // < nb * batch <= n_records
@@ -128,6 +137,24 @@ __global__ __launch_bounds__(256) void input_aug_kernel(const uint8_t* __restric
     ox = (int)(r.y % span);
     flip = (int)(r.z & 1u);
   }
+  return AugDraw{rec, oy, ox, flip};
+}
+
+// Input pipeline of a training step: sample j = blockIdx.y takes the record of aug_draw, shifted by
+// (oy - pad, ox - pad) with black padding and mirrored when flip.  A thread then does what
+// input_norm's does, for up to AUG_PX pixels of the image: three byte loads (none for padding),
+// one 16-B store.
+__global__ __launch_bounds__(256) void input_aug_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ lab,
+                                                        const int* __restrict__ cursor, uint32_t n_records,
+                                                        uint32_t batch, int H, int W, int pad, int flags, int half_bits,
+                                                        uint32_t k0, uint32_t k1, uint16_t* __restrict__ y,
+                                                        uint8_t* __restrict__ lab_out, int* __restrict__ params_out,
+                                                        NormCoef c) {
+  const uint32_t j = blockIdx.y;
+  const uint32_t t = (uint32_t)*cursor;  // a non-negative int32
+  const AugDraw d = aug_draw(j, t, n_records, batch, pad, flags, half_bits, k0, k1);
+  const uint32_t rec = d.rec;
+  const int oy = d.oy, ox = d.ox, flip = d.flip;
   const int p0 = blockIdx.x * (256 * AUG_PX) + threadIdx.x;
   if (p0 == 0) {
     if (params_out) *reinterpret_cast<int4*>(params_out + 4 * j) = make_int4((int)rec, oy, ox, flip);
@@ -150,6 +177,102 @@ __global__ __launch_bounds__(256) void input_aug_kernel(const uint8_t* __restric
       v2 = s[2];
     }
     *reinterpret_cast<short8_t*>(dst + (long)p * 8) = norm_pack8(v0, v1, v2, c);
+  }
+}
+
+// Entries of one mix table (data/augment.py MIX_L): the index is the top 12 bits of a Philox word.
+constexpr int MIX_L = 4096;
+
+// One augmented pixel of a sample, as input_aug reads it: u8 channels in the low three bytes.
+__device__ __forceinline__ uint32_t aug_pixel(const uint8_t* __restrict__ src, const AugDraw& d, int py, int px,
+                                              int H, int W, int pad) {
+  const int sy = py + d.oy - pad, sx = (d.flip ? W - 1 - px : px) + d.ox - pad;
+  uint32_t v = 0;  // outside the image: black
+  if ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) {
+    const uint8_t* s = src + ((long)sy * W + sx) * 3;
+    v = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16;
+  }
+  return v;
+}
+
+// input_aug followed by mixup or CutMix (data/augment.py): the batch draws M = Philox(t, 0, 0;
+// stream 3) and Nn = Philox(t, 1, 0; stream 3); sample j mixes with sample pj = (j + r) % B of the
+// same batch, r = 1 + M.y % (B - 1), taken after its own shuffle / crop / flip.  table is
+// int32 [2][MIX_L], row 0 mixup's and row 1 CutMix's, entry M.x >> 20 packing k = round(256 lambda)
+// (low half) and c = round(256 sqrt(1 - lambda)) (high half).  Mixup: every channel is
+// (k ua + (256 - k) ub) / 256, exact in fp32; CutMix: a (W c + 128 >> 8) x (H c + 128 >> 8) box
+// centred at (Nn.x % W, Nn.y % H), clipped, shows the partner.  All of this and both samples'
+// aug_draw are uniform in the workgroup: scalar registers.  modes: 1 = mixup, 2 = CutMix, 3 = the
+// batch is CutMix when M.z & 1.  mix_out row j: (pj, num, den, mode, x0, y0, x1, y1), num / den the
+// weight of the partner's label.
+__global__ __launch_bounds__(256) void input_mix_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ lab,
+                                                        const int* __restrict__ cursor, uint32_t n_records,
+                                                        uint32_t batch, int H, int W, int pad, int flags, int half_bits,
+                                                        uint32_t k0, uint32_t k1, const int* __restrict__ table,
+                                                        int modes, uint16_t* __restrict__ y,
+                                                        uint8_t* __restrict__ lab_out, int* __restrict__ params_out,
+                                                        int* __restrict__ mix_out, NormCoef c) {
+  const uint32_t j = blockIdx.y;
+  const uint32_t t = (uint32_t)*cursor;  // a non-negative int32
+  const U4 m = philox4x32_10(t, 0u, 0u, 3u, k0, k1);
+  const uint32_t pj = (j + 1u + m.y % (batch - 1u)) % batch;  // batch >= 2 (sl_input_mix)
+  const int mode = modes == 3 ? ((m.z & 1u) ? 2 : 1) : modes;
+  const uint32_t entry = (uint32_t)table[(mode - 1) * MIX_L + (int)(m.x >> 20)];
+  const AugDraw da = aug_draw(j, t, n_records, batch, pad, flags, half_bits, k0, k1);
+  const AugDraw db = aug_draw(pj, t, n_records, batch, pad, flags, half_bits, k0, k1);
+  int k = 256, x0 = 0, y0 = 0, x1 = 0, y1 = 0, num, den;
+  if (mode == 1) {
+    k = min((int)(entry & 0xFFFFu), 256);
+    num = 256 - k;
+    den = 256;
+  } else {
+    const U4 nn = philox4x32_10(t, 1u, 0u, 3u, k0, k1);
+    const int cc = min((int)(entry >> 16), 256);
+    const int bw = (W * cc + 128) >> 8, bh = (H * cc + 128) >> 8;
+    if (bw > 0 && bh > 0) {
+      const int bx = (int)(nn.x % (uint32_t)W) - bw / 2, by = (int)(nn.y % (uint32_t)H) - bh / 2;
+      x0 = max(bx, 0);
+      x1 = min(bx + bw, W);
+      y0 = max(by, 0);
+      y1 = min(by + bh, H);
+    }
+    num = (x1 - x0) * (y1 - y0);
+    den = H * W;
+  }
+  const int p0 = blockIdx.x * (256 * AUG_PX) + threadIdx.x;
+  if (p0 == 0) {
+    if (params_out) *reinterpret_cast<int4*>(params_out + 4 * j) = make_int4((int)da.rec, da.oy, da.ox, da.flip);
+    if (mix_out) {
+      *reinterpret_cast<int4*>(mix_out + 8 * j) = make_int4((int)pj, num, den, mode);
+      *reinterpret_cast<int4*>(mix_out + 8 * j + 4) = make_int4(x0, y0, x1, y1);
+    }
+    if (lab_out) lab_out[j] = lab[da.rec];
+  }
+  const int img = H * W;
+  const uint8_t* srca = x + (long)da.rec * img * 3;
+  const uint8_t* srcb = x + (long)db.rec * img * 3;
+  uint16_t* dst = y + (long)j * img * 8;
+#pragma unroll
+  for (int q = 0; q < AUG_PX; ++q) {
+    const int p = p0 + q * 256;
+    if (p >= img) break;
+    const int py = p / W, px = p - py * W;
+    float f0, f1, f2;
+    if (mode == 1) {
+      const uint32_t ua = aug_pixel(srca, da, py, px, H, W, pad), ub = aug_pixel(srcb, db, py, px, H, W, pad);
+      const int kb = 256 - k;
+      // n = k ua + (256 - k) ub <= 65280: n / 256 is exact in fp32
+      f0 = (float)(k * (int)(ua & 255u) + kb * (int)(ub & 255u)) * (1.f / 256.f);
+      f1 = (float)(k * (int)((ua >> 8) & 255u) + kb * (int)((ub >> 8) & 255u)) * (1.f / 256.f);
+      f2 = (float)(k * (int)(ua >> 16) + kb * (int)(ub >> 16)) * (1.f / 256.f);
+    } else {
+      const bool in = px >= x0 && px < x1 && py >= y0 && py < y1;  // the partner's pixel at (y, x)
+      const uint32_t u = aug_pixel(in ? srcb : srca, in ? db : da, py, px, H, W, pad);
+      f0 = (float)(u & 255u);
+      f1 = (float)((u >> 8) & 255u);
+      f2 = (float)(u >> 16);
+    }
+    *reinterpret_cast<short8_t*>(dst + (long)p * 8) = norm_pack8(f0, f1, f2, c);
   }
 }
 
@@ -622,10 +745,17 @@ __device__ unsigned g_dbias_ticket;
 // 16-lane group.  dlogits (bf16, [N][ldd], zero beyond ncls) are scaled by
 // grad_scale; the bias gradient (sum over rows of dlogits) is folded per
 // workgroup and added atomically.
+// SOFT: the target of row i is q_c = (1 - eps)(wa [c = la] + wb [c = lb]) + eps / ncls instead of
+// one-hot la = lab[i]: row i of mix (int32 [N][8], input_mix's mix_out; null = smoothing alone) names
+// the partner pj and its weight wb = num / den, lb = lab[pj], wa = 1 - wb.  loss = logsumexp(z) -
+// sum_c q_c z_c, dz = (softmax(z) - q) grad_scale; correct stays argmax against la.
+// The soft form's two extra arguments, (const int* mix, float eps), are a trailing pack that is
+// empty for the one-hot form, whose argument list and code are then exactly what they were.
+template <bool SOFT, class... Soft>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ z, const uint8_t* __restrict__ lab,
                                                          float* __restrict__ loss, float* __restrict__ correct,
                                                          uint16_t* __restrict__ dz, int ldd, float* __restrict__ dbias,
-                                                         int N, int ncls, float grad_scale) {
+                                                         int N, int ncls, float grad_scale, Soft... soft) {
   __shared__ float bsum[16][16];
   const int tid = threadIdx.x, c = tid & 15, grp = tid >> 4;
   const int row = blockIdx.x * 16 + grp;
@@ -645,7 +775,27 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     s += __shfl_xor(s, 8);
     int l = lab[row];
     l = l < ncls ? l : 0;
-    const float zl = __shfl(v, (tid & 63 & ~15) | l);
+    float zl, q = 0.f;
+    if constexpr (SOFT) {
+      const auto [mix, eps] = std::tuple<const int*, float>(soft...);
+      int lb = l;
+      float wb = 0.f;
+      if (mix) {
+        const int pj = mix[8 * row];
+        lb = (unsigned)pj < (unsigned)N ? lab[pj] : l;
+        lb = lb < ncls ? lb : 0;
+        wb = (float)mix[8 * row + 1] / (float)mix[8 * row + 2];
+      }
+      // lanes beyond ncls hold -inf: they take no part in sum_c q_c z_c
+      q = c < ncls ? (1.f - eps) * ((c == l ? 1.f - wb : 0.f) + (c == lb ? wb : 0.f)) + eps / (float)ncls : 0.f;
+      zl = c < ncls ? q * v : 0.f;
+      zl += __shfl_xor(zl, 1);
+      zl += __shfl_xor(zl, 2);
+      zl += __shfl_xor(zl, 4);
+      zl += __shfl_xor(zl, 8);
+    } else {
+      zl = __shfl(v, (tid & 63 & ~15) | l);
+    }
     int idx = v == mx ? c : 16;
     idx = min(idx, __shfl_xor(idx, 1));
     idx = min(idx, __shfl_xor(idx, 2));
@@ -655,7 +805,8 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
       if (loss) loss[row] = mx + __logf(s) - zl;
       if (correct) correct[row] = idx == l ? 1.f : 0.f;
     }
-    dv = c < ncls ? (e / s - (c == l ? 1.f : 0.f)) * grad_scale : 0.f;
+    if constexpr (SOFT) dv = c < ncls ? (e / s - q) * grad_scale : 0.f;
+    else dv = c < ncls ? (e / s - (c == l ? 1.f : 0.f)) * grad_scale : 0.f;
     if (c < ldd) dz[(long)row * ldd + c] = f2bf(dv);
   }
   bsum[grp][c] = dv;
@@ -732,6 +883,28 @@ int sl_input_aug(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_
                      stream, x, lab, cursor,
                      (uint32_t)n_records, (uint32_t)batch, H, W, pad, flags, half_bits, (uint32_t)seed,
                      (uint32_t)(seed >> 32), y, lab_out, params_out, norm_coef(m0, m1, m2, s0, s1, s2));
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// sl_input_aug followed by mixup / CutMix with another sample of the batch.  table: int32 [2][4096]
+// (mixup's row, CutMix's row); modes: 1 = mixup, 2 = CutMix, 3 = either, drawn per batch.  mix_out:
+// int32 [batch][8].  Reads cursor and table on the device: a captured graph replays it.
+int sl_input_mix(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_records, int batch, int H, int W,
+                 int pad, int flags, unsigned long long seed, const int* table, int modes, uint16_t* y,
+                 uint8_t* lab_out, int* params_out, int* mix_out, float m0, float m1, float m2, float s0, float s1,
+                 float s2, hipStream_t stream) {
+  if (!x || !cursor || !y || !table || (lab_out && !lab)) return -2;
+  if (batch < 2 || batch > 65535 || n_records < batch || H < 1 || W < 1 || (long)H * W > (1L << 22)) return -1;
+  if (pad < 0 || pad >= H || pad >= W || (flags & ~3) || modes < 1 || modes > 3) return -1;
+  int bits = 0;  // the Feistel network's half width, as in sl_input_aug
+  while (bits < 32 && ((unsigned long long)(n_records - 1) >> bits)) ++bits;
+  if (bits < 2) bits = 2;
+  const int half_bits = (bits + 1) / 2;
+  hipLaunchKernelGGL(input_mix_kernel, dim3((H * W + 256 * AUG_PX - 1) / (256 * AUG_PX), batch), dim3(256), 0,
+                     stream, x, lab, cursor, (uint32_t)n_records, (uint32_t)batch, H, W, pad, flags, half_bits,
+                     (uint32_t)seed, (uint32_t)(seed >> 32), table, modes, y, lab_out, params_out, mix_out,
+                     norm_coef(m0, m1, m2, s0, s1, s2));
   SL_CHECK_LAUNCH();
   return 0;
 }
@@ -876,8 +1049,20 @@ int sl_avgpool_bwd(const uint16_t* dy, uint16_t* dx, int N, int HW, int C, hipSt
 int sl_softmax_ce(const float* z, const uint8_t* lab, float* loss, float* correct, uint16_t* dz, int ldd,
                   float* dbias, int N, int ncls, float grad_scale, hipStream_t stream) {
   if (ncls > 16 || ldd > 16 || ldd < ncls) return -1;
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, z, lab, loss, correct, dz, ldd,
+  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3((N + 15) / 16), dim3(256), 0, stream, z, lab, loss, correct, dz, ldd,
                      dbias, N, ncls, grad_scale);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// Soft-target form: mix (int32 [N][8], nullable) pairs each row with a partner row and its weight,
+// eps is the label smoothing; with mix null and eps 0 it computes what sl_softmax_ce does.
+int sl_softmax_ce_soft(const float* z, const uint8_t* lab, float* loss, float* correct, uint16_t* dz, int ldd,
+                       float* dbias, int N, int ncls, float grad_scale, const int* mix, float eps,
+                       hipStream_t stream) {
+  if (ncls > 16 || ncls < 1 || ldd > 16 || ldd < ncls || !(eps >= 0.f && eps < 1.f)) return -1;
+  hipLaunchKernelGGL((softmax_ce_kernel<true, const int*, float>), dim3((N + 15) / 16), dim3(256), 0, stream, z, lab, loss, correct, dz,
+                     ldd, dbias, N, ncls, grad_scale, mix, eps);
   SL_CHECK_LAUNCH();
   return 0;
 }

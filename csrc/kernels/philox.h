@@ -1,6 +1,7 @@
 // Counter-based Philox4x32-10, shared by the shard generator (datagen.hip) and the input
-// pipeline (cnn_aux.hip input_aug_kernel).  The fourth counter word names the stream, so two
-// users never collide under one seed: 0 = shard generation, 1 = epoch shuffle, 2 = crop / flip.
+// pipeline (cnn_aux.hip input_aug_kernel, input_mix_kernel).  The fourth counter word names the
+// stream, so two users never collide under one seed: 0 = shard generation, 1 = epoch shuffle,
+// 2 = crop / flip, 3 = mixup / CutMix.
 // numpy twin: serverless_learn_amd/data/device_synth.py philox4x32_10.
 #pragma once
 #include <stdint.h>

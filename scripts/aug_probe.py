@@ -1,10 +1,13 @@
 #!/usr/bin/env python
-"""What the ResNet engine's input pipeline costs (profiles/r13_input).
+"""What the ResNet engine's input pipeline costs (profiles/r13_input), and what label smoothing,
+mixup and CutMix add to it (profiles/r14_mix).
 
-Two measurements, each a process of its own so that each runs under its own time limit:
+Four measurements, each a process of its own so that each runs under its own time limit:
 
     timeout -k 10 300 python scripts/aug_probe.py kernel --out profiles/r13_input && \\
     timeout -k 10 600 python scripts/aug_probe.py step --out profiles/r13_input
+    timeout -k 10 300 python scripts/aug_probe.py mix --out profiles/r14_mix && \\
+    timeout -k 10 900 python scripts/aug_probe.py mix_step --out profiles/r14_mix
 
 kernel  input_norm_kernel and input_aug_kernel with each combination of parts on (aug_off: neither,
         which no trainer launches -- the cost of the per-image layout alone), B = 1024 images
@@ -14,6 +17,13 @@ kernel  input_norm_kernel and input_aug_kernel with each combination of parts on
 step    the graph-replayed ResNet-18 step at B = 1024 with shuffle + crop-flip on against off,
         alternating three times each; the question is whether the difference lies within the off
         runs' min-max spread.
+
+mix     input_mix_kernel (mixup, CutMix, either; shuffle + crop-flip on) against input_aug with both
+        parts on and input_norm, and softmax_ce_soft (smoothing alone, with mixup rows) against
+        softmax_ce at B = 1024, ten classes: the same interleaved rounds.  The old kernels are
+        unchanged code in the same library, so they are the baseline.
+mix_step  the graph-replayed step with each of label_smoothing, mixup_alpha, cutmix_alpha on, and all
+        three on top of shuffle + crop-flip, against all off: alternating, three runs each.
 
 Each prints one JSON line and writes it to <out>/aug_probe_<what>.json.
 """
@@ -114,15 +124,93 @@ def step(args) -> dict:
     return res
 
 
+MIX_VARIANTS = (("mix_mixup", dict(mixup=True)), ("mix_cutmix", dict(cutmix=True)),
+                ("mix_either", dict(mixup=True, cutmix=True)))
+
+
+def mix(args) -> dict:
+    from serverless_learn_amd.data import augment as A
+    from serverless_learn_amd.models.resnet import CIFAR_MEAN, CIFAR_STD
+    from serverless_learn_amd.ops import cnn as K
+
+    dev = torch.device("cuda:0")
+    x, y = _shard(dev)
+    out = torch.empty(B, HW, HW, 8, dtype=torch.bfloat16, device=dev)
+    lab = torch.empty(B, dtype=torch.uint8, device=dev)
+    params = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    mix_out = torch.zeros(B, 8, dtype=torch.int32, device=dev)
+    table = torch.from_numpy(A.mix_tables(0.4, 1.0)).to(dev)
+    cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+    both = dict(shuffle=True, augment="crop-flip")
+    fns = {"input_norm": lambda: K.input_norm(x, y, cursor, B, out, lab, CIFAR_MEAN, CIFAR_STD),
+           "aug_both": lambda: K.input_aug(x, y, cursor, B, out, lab, params, CIFAR_MEAN, CIFAR_STD, seed=0, pad=4,
+                                           **both)}
+    for name, kw in MIX_VARIANTS:
+        fns[name] = (lambda kw: lambda: K.input_mix(x, y, cursor, B, out, lab, params, mix_out, table, CIFAR_MEAN,
+                                                    CIFAR_STD, seed=0, pad=4, **both, **kw))(kw)
+    z = torch.randn(B, 10, device=dev) * 3
+    loss, corr = torch.zeros(B, device=dev), torch.zeros(B, device=dev)
+    dz = torch.zeros(B, 16, dtype=torch.bfloat16, device=dev)
+    db = torch.zeros(10, device=dev)
+    fns["softmax_ce"] = lambda: K.softmax_ce(z, lab, loss, corr, dz, db, 1.0 / B)
+    fns["soft_smoothing"] = lambda: K.softmax_ce_soft(z, lab, loss, corr, dz, db, 1.0 / B, mix=None, eps=0.1)
+    fns["soft_mix"] = lambda: K.softmax_ce_soft(z, lab, loss, corr, dz, db, 1.0 / B, mix=mix_out, eps=0.1)
+    fns["mix_mixup"]()  # mix_out rows for soft_mix
+    for fn in fns.values():
+        _timed(fn, 20)
+    us = {name: [] for name in fns}
+    for r in range(args.rounds):
+        cursor.fill_(5 * r + 1)
+        for name, fn in fns.items():
+            us[name].append(1e3 * _timed(fn, args.launches))
+    res = {"what": "mix", "batch": B, "hw": HW, "records": N, "launches": args.launches, "rounds": args.rounds,
+           "device": torch.cuda.get_device_name(0)}
+    for name, v in us.items():
+        res[name] = {"us_median": round(statistics.median(v), 3), "us_min": round(min(v), 3),
+                     "us_max": round(max(v), 3), "us_rounds": [round(t, 3) for t in v]}
+    return res
+
+
+def mix_step(args) -> dict:
+    from serverless_learn_amd.models.resnet_engine import FusedResNetTrainer
+
+    dev = torch.device("cuda:0")
+    x, y = _shard(dev)
+    cases = (("off", {}), ("smoothing", dict(label_smoothing=0.1)), ("mixup", dict(mixup_alpha=0.4)),
+             ("cutmix", dict(cutmix_alpha=1.0)),
+             ("all", dict(label_smoothing=0.1, mixup_alpha=0.4, cutmix_alpha=1.0, shuffle=True, augment="crop-flip")))
+    trainers = {}
+    for name, kw in cases:
+        tr = FusedResNetTrainer(batch=B, device=dev, seed=0, **kw)
+        tr.load_shard(x, y)
+        tr.step()
+        tr.capture(warmup=1)
+        _timed(tr.step, 10)
+        trainers[name] = tr
+    ms = {name: [] for name in trainers}
+    for _ in range(3):
+        for name, tr in trainers.items():
+            ms[name].append(_timed(tr.step, args.steps))
+    res = {"what": "mix_step", "batch": B, "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    for name, v in ms.items():
+        res[name] = {"ms_runs": [round(t, 4) for t in v], "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                     "ms_median": round(statistics.median(v), 4), "loss": round(trainers[name].stats().loss, 4)}
+    res["off_spread_ms"] = round(res["off"]["ms_max"] - res["off"]["ms_min"], 4)
+    for name in ms:
+        if name != "off":
+            res[name]["minus_off_ms"] = round(res[name]["ms_median"] - res["off"]["ms_median"], 4)
+    return res
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("what", choices=["kernel", "step"])
+    ap.add_argument("what", choices=["kernel", "step", "mix", "mix_step"])
     ap.add_argument("--out", default="")
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=60)
     args = ap.parse_args(argv)
-    res = kernel(args) if args.what == "kernel" else step(args)
+    res = {"kernel": kernel, "step": step, "mix": mix, "mix_step": mix_step}[args.what](args)
     line = json.dumps(res)
     print(line)
     if args.out:

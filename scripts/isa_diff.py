@@ -5,9 +5,11 @@ revision and the working tree, for the default and the -DSL_DETERMINISTIC=1 buil
   scripts/isa_diff.py [REV] [old=new ...] [--loose | --mix]
 
 Prints SAME / DIFF / GONE / NEW per kernel; exits 1 on any DIFF or NEW.  `old=new` maps a
-renamed (mangled) kernel.  --loose is the check for a kernel whose parameter list changed: the
-scalar kernarg loads, waits and scalar register numbers are dropped and, of the descriptor, only
-VGPR count, accum offset and private segment size must be equal and the LDS size no larger.
+renamed (mangled) kernel, such as one that became a template instantiation; the section a kernel
+is placed in (a template's own comdat section) is not compared.  --loose is the check for a kernel
+whose parameter list changed: the scalar kernarg loads, waits and scalar register numbers are
+dropped and, of the descriptor, only VGPR count, accum offset and private segment size must be
+equal and the LDS size no larger.
 --mix is the check for a kernel whose source was rearranged without changing what it does: those
 descriptor fields again, and the number of instructions in each of the classes MUST (matrix, LDS,
 buffer and global loads / stores / atomics, barriers) must be equal; such a kernel prints MIX with
@@ -18,7 +20,8 @@ import concurrent.futures as cf, glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
          "-Wno-unused-command-line-argument", "--cuda-device-only", "-S", "-o", "-"]
-NORM = [(r"__hip_cuid_\w+", "__hip_cuid"), (r"(\.LBB|\.Lfunc_end|BB)\d+", r"\1"), (r"\s*;.*", "")]
+NORM = [(r"__hip_cuid_\w+", "__hip_cuid"), (r"(\.LBB|\.Lfunc_end|BB)\d+", r"\1"), (r"\s*;.*", ""),
+        (r"(?m)^\s*\.(text|section)\b.*", "")]  # where the code is placed (a template's comdat section) is not code
 KEEP = ("next_free_vgpr", "accum_offset", "private_segment_fixed_size")
 MUST = ("v_mfma", "ds_", "buffer_load", "buffer_store", "buffer_atomic", "global_load", "global_store", "global_atomic",
         "buffer_", "global_", "s_barrier")  # first match: the bare buffer_ / global_ count the rest (cache control)

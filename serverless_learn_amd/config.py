@@ -71,6 +71,9 @@ class Config:
     augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip, data/augment.py)
     augment_pad: int = 4               # crop-flip: black pixels of padding around the image the crop is taken from
     shuffle: bool = False              # resnet18: draw each epoch's records through a fresh permutation of the shard
+    label_smoothing: float = 0.0       # resnet18: smooth the training targets by this much (0 <= eps < 1)
+    mixup_alpha: float = 0.0           # resnet18: mixup with lambda ~ Beta(alpha, alpha) per batch (0 = off)
+    cutmix_alpha: float = 0.0          # resnet18: CutMix likewise; with both on, one of the two per batch
     seed: int = 0
     checkpoint_every: int = 0          # steps between checkpoints (rank 0); 0 = off
     max_steps: int = 0                 # 0 = run until stopped
@@ -99,11 +102,19 @@ class Config:
         self.validate()
 
     def validate(self) -> None:
-        """Refuse combinations no component implements (the input pipeline's and the top-k sparse
-        gossip's)."""
+        """Refuse combinations no component implements (the input pipeline's, the soft-target loss's
+        and the top-k sparse gossip's)."""
         if (self.augment, self.augment_pad, self.shuffle) != ("none", 4, False) and self.model in ("mlp", "simulate"):
             # the MLP kernels read X from bricks tiled once per shard: a per-sample gather would undo that
             raise ValueError(f"augment / shuffle: the {self.model} model has no input pipeline (model='resnet18')")
+        if (self.label_smoothing, self.mixup_alpha, self.cutmix_alpha) != (0, 0, 0):  # NaN included
+            from .data.augment import check_mix
+
+            check_mix(self.label_smoothing, self.mixup_alpha, self.cutmix_alpha)
+            if self.model in ("mlp", "simulate"):
+                # the MLP rows kernel fuses its own one-hot loss and reads X from bricks tiled once per shard
+                raise ValueError(f"label_smoothing / mixup_alpha / cutmix_alpha: the {self.model} model has neither "
+                                 "a soft-target loss nor an input pipeline (model='resnet18')")
         x = self.gossip_topk
         if x == 0:
             return

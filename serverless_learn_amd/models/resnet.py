@@ -235,11 +235,13 @@ def ref_forward(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, traini
 
 
 def ref_grads(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, y: torch.Tensor, grad_scale: float,
-              running: dict | None = None):
-    """(loss_sum, correct, grad_flat) with d(loss_i)/dlogits scaled by grad_scale."""
+              running: dict | None = None, targets: torch.Tensor | None = None):
+    """(loss_sum, correct, grad_flat) with d(loss_i)/dlogits scaled by grad_scale.  ``x_u8`` is in
+    pixel units (u8, or float after a mix); ``targets`` ([B, classes] probabilities) replaces the
+    one-hot ``y`` in the loss, and ``correct`` stays the argmax against ``y``."""
     w = flat.detach().clone().float().requires_grad_(True)
     logits = ref_forward(spec, w, x_u8, True, running)
-    losses = F.cross_entropy(logits, y.long(), reduction="none")
+    losses = F.cross_entropy(logits, y.long() if targets is None else targets.to(logits.dtype), reduction="none")
     (losses.sum() * grad_scale).backward()
     correct = (logits.argmax(1) == y.long()).float().sum()
     return losses.detach().sum(), correct.detach(), w.grad.detach()
@@ -251,16 +253,22 @@ class CPUResNetTrainer(OptStateCPU):
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 5e-4,
                  seed: int = 0, world_size: int = 1, stem: str = "cifar", flat: torch.Tensor | None = None,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
-                 **opt):
+                 label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, **opt):
         from ..data import augment as A
         from .mlp import StepStats, sgd_update  # noqa: F401
 
         self.spec = resnet18_spec(stem, 10, in_hw)
         A.check(augment, augment_pad, self.spec.in_hw)
+        A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         # the training input pipeline (data/augment.py), keyed on (seed, cursor, sample) like the
         # GPU engine's; last_aug is the last batch's (record, oy, ox, flip), None with it off
         self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
         self.last_aug = None
+        # label smoothing, mixup and CutMix (data/augment.py); last_mix is the last batch's
+        # (partner, num, den, mode, x0, y0, x1, y1), None with no mix.  Under mixing the accuracy
+        # that stats() reports is against each sample's own label: a diagnostic
+        self.label_smoothing, self.mixup_alpha, self.cutmix_alpha = label_smoothing, mixup_alpha, cutmix_alpha
+        self.last_mix = None
         self.batch = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
@@ -299,9 +307,10 @@ class CPUResNetTrainer(OptStateCPU):
         self.n_batches = self.x.shape[0] // self.batch
 
     def step(self) -> None:
-        if self.shuffle or self.augment != "none":
-            from ..data import augment as A
+        from ..data import augment as A
 
+        mixes = self.mixup_alpha > 0 or self.cutmix_alpha > 0
+        if self.shuffle or self.augment != "none" or mixes:
             self.last_aug = A.batch_params(self.seed, self.cursor, self.x.shape[0], self.batch, self.augment_pad,
                                            self.shuffle, self.augment)
             xs = torch.from_numpy(A.apply(self.x.cpu().numpy(), self.last_aug, self.augment_pad))
@@ -310,8 +319,17 @@ class CPUResNetTrainer(OptStateCPU):
             b = self.cursor % self.n_batches
             xs = self.x[b * self.batch:(b + 1) * self.batch]
             ys = self.y[b * self.batch:(b + 1) * self.batch]
+        targets = None
+        if mixes:
+            hw = self.spec.in_hw
+            self.last_mix = A.mix_params(self.seed, self.cursor, self.batch, hw, hw, self.mixup_alpha,
+                                         self.cutmix_alpha)
+            xs = torch.from_numpy(A.mix_apply(xs.numpy(), self.last_mix))
+        if mixes or self.label_smoothing > 0:
+            targets = torch.from_numpy(A.soft_targets(ys.cpu().numpy(), self.last_mix, self.label_smoothing,
+                                                      self.spec.classes))
         loss, correct, g = ref_grads(self.spec, self.params, xs, ys, 1.0 / (self.batch * self.world_size),
-                                     self.running)
+                                     self.running, targets)
         self.phases.mark("compute")
         if self.allreduce is not None:
             self.allreduce(g)

@@ -8,10 +8,12 @@ and replayed with zero host work (the data batch is chosen by a device-side
 cursor, like the MLP engine).
 
 Per step:
-  forward   input_norm (input_aug with shuffle= / augment= on: data/augment.py) ->
+  forward   input_norm (input_aug with shuffle= / augment= on, input_mix with mixup_alpha= /
+            cutmix_alpha= on: data/augment.py) ->
             [conv (+BN stats in the epilogue) -> bn_apply with
             the finalize folded in (+residual, ReLU)] x 20 -> avgpool -> fc ->
-            softmax-CE (loss, dlogits, dbias); a 64-channel block's conv2 applies
+            softmax-CE (loss, dlogits, dbias; against soft targets with a mix or
+            label_smoothing= on); a 64-channel block's conv2 applies
             relu(bn1(.)) while loading c1 instead (BN-on-load, no a1 pass)
   backward  per block, in reverse: bn_bwd_apply (ReLU mask fused), conv wgrad
             (split-K partials in a slab + one ordered reduce into the flat
@@ -80,7 +82,7 @@ class FusedResNetTrainer(GraphSlots):
                  weight_decay: float = 5e-4, seed: int = 0, world_size: int = 1, stem: str = "cifar",
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
-                 **opt):
+                 label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, **opt):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
@@ -88,11 +90,15 @@ class FusedResNetTrainer(GraphSlots):
 
         self.spec = spec = resnet18_spec(stem, classes, in_hw)
         A.check(augment, augment_pad, spec.in_hw)
+        A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         _native.lib()
         self.K, self.O = K, O
         # the training input pipeline (data/augment.py): a pure function of (seed, cursor, sample),
         # so the cursor that is checkpointed and broadcast already is all the state it has
         self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
+        # label smoothing, mixup and CutMix of the training loss / input, keyed the same way
+        self.label_smoothing, self.mixup_alpha, self.cutmix_alpha = label_smoothing, mixup_alpha, cutmix_alpha
+        self.mixes = mixup_alpha > 0 or cutmix_alpha > 0
         dev = self.device = torch.device(device)
         self.batch = B = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
@@ -145,10 +151,18 @@ class FusedResNetTrainer(GraphSlots):
         hw = spec.in_hw
         self.x0 = torch.empty(B, hw, hw, 8, **bf)
         self.labels = torch.zeros(B, dtype=torch.uint8, device=dev)
-        # (record, oy, ox, flip) of every sample of the last training batch, written by input_aug;
-        # None with the pipeline off (input_norm feeds the network, as in every evaluation path)
+        # (record, oy, ox, flip) of every sample of the last training batch, written by input_aug /
+        # input_mix; None with the pipeline off (input_norm feeds the network, as in every
+        # evaluation path)
         self.aug_out = (torch.zeros(B, 4, dtype=torch.int32, device=dev)
-                        if self.shuffle or augment != "none" else None)
+                        if self.shuffle or augment != "none" or self.mixes else None)
+        # (partner, num, den, mode, x0, y0, x1, y1) of every sample of the last training batch, written
+        # by input_mix and read by the soft-target loss; None with no mix.  mix_tab: the lambda
+        # quantiles of each mode, built once (data/augment.py mix_tables)
+        self.mix_out = self.mix_tab = None
+        if self.mixes:
+            self.mix_out = torch.zeros(B, 8, dtype=torch.int32, device=dev)
+            self.mix_tab = torch.from_numpy(A.mix_tables(mixup_alpha, cutmix_alpha)).to(dev)
         # ---- stem buffers ----
         sc = spec.stem_conv
         s_hw = K.out_size(hw, sc.k, sc.stride, sc.pad)
@@ -276,7 +290,12 @@ class FusedResNetTrainer(GraphSlots):
     def forward(self, train: bool = True):
         K, spec = self.K, self.spec
         self.arena.zero_()
-        if train and self.aug_out is not None:
+        if train and self.mixes:
+            K.input_mix(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, self.aug_out, self.mix_out,
+                        self.mix_tab, CIFAR_MEAN, CIFAR_STD, seed=self.seed, shuffle=self.shuffle,
+                        augment=self.augment, pad=self.augment_pad, mixup=self.mixup_alpha > 0,
+                        cutmix=self.cutmix_alpha > 0)
+        elif train and self.aug_out is not None:
             K.input_aug(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, self.aug_out, CIFAR_MEAN,
                         CIFAR_STD, seed=self.seed, shuffle=self.shuffle, augment=self.augment,
                         pad=self.augment_pad)
@@ -318,8 +337,15 @@ class FusedResNetTrainer(GraphSlots):
                                  mask_out=st["ym"])
         K.avgpool_fwd(self.feat_in, self.feat)
         K.conv_fwd(self.feat, self.fc_w, spec.classes, 1, 1, 0, yf=self.logits, bias=self.fc_b)
-        K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
-                     self.fc_gb if train else None, self.grad_scale)
+        if train and (self.mixes or self.label_smoothing > 0):
+            # soft targets; `correct` stays the argmax against the sample's own label (a diagnostic
+            # under mixing)
+            K.softmax_ce_soft(self.logits, self.labels, self.loss, self.correct,
+                              self.dlogits.view(self.batch, LOGIT_LD), self.fc_gb, self.grad_scale,
+                              mix=self.mix_out, eps=self.label_smoothing)
+        else:
+            K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
+                         self.fc_gb if train else None, self.grad_scale)
 
     def backward(self):
         K, spec = self.K, self.spec

@@ -27,6 +27,7 @@ N.register("sl_conv_wt", [P, I, L, P])
 N.register("sl_conv_wt_desc_size", [])
 N.register("sl_input_norm", [P, P, P, I, I, L, P, P, F, F, F, F, F, F, P])
 N.register("sl_input_aug", [P, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P, P, F, F, F, F, F, F, P])
+N.register("sl_input_mix", [P, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, I, P, P, P, P, F, F, F, F, F, F, P])
 N.register("sl_cursor_bump", [P, P])
 N.register("sl_bn_finalize", [P, P, P, P, P, P, I, F, F, F, P])
 N.register("sl_bn_apply", [P, P, P, P, P, L, I, I, I, P])
@@ -44,6 +45,7 @@ N.register("sl_maxpool_bwd", [P, P, P, I, I, I, I, I, I, I, I, I, P])
 N.register("sl_avgpool_fwd", [P, P, I, I, I, P])
 N.register("sl_avgpool_bwd", [P, P, I, I, I, P])
 N.register("sl_softmax_ce", [P, P, P, P, P, I, P, I, I, F, P])
+N.register("sl_softmax_ce_soft", [P, P, P, P, P, I, P, I, I, F, P, F, P])
 N.register("sl_wgrad_side_begin", [P])
 N.register("sl_wgrad_side_join", [P, I])
 N.register("sl_conv3x3_c64_applicable", [I, I, I, I, I, I, I, I, I])
@@ -346,6 +348,35 @@ def input_aug(x_u8, labels, cursor, batch: int, y, lab_out, params_out, mean, st
            *[float(v) for v in std], N.stream_ptr())
 
 
+def input_mix(x_u8, labels, cursor, batch: int, y, lab_out, params_out, mix_out, table, mean, std, seed: int = 0,
+              shuffle: bool = False, augment: str = "none", pad: int = 4, mixup: bool = False, cutmix: bool = False):
+    """:func:`input_aug` followed by mixup and / or CutMix (data/augment.py): every sample of the batch
+    at ``cursor`` is blended with (``mixup``) or shows a box of (``cutmix``) another sample of the same
+    batch, both taken after their own shuffle / crop / flip; with both on the mode is drawn per batch.
+    ``table`` (int32 [2, 4096], data/augment.py ``mix_tables``) holds the lambda quantiles of each mode.
+    ``params_out`` is :func:`input_aug`'s; ``mix_out`` (int32 [batch, 8]) receives each sample's
+    (partner, num, den, mode, x0, y0, x1, y1), num / den the weight of the partner's label."""
+    from ..data import augment as A
+
+    assert x_u8.dtype == torch.uint8 and x_u8.shape[-1] == 3 and y.shape[-1] == 8 and x_u8.is_contiguous()
+    n, h, w = x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]
+    A.check(augment, pad, min(h, w))
+    if not (mixup or cutmix):
+        raise ValueError("input_mix: neither mixup nor cutmix is on (input_aug is the unmixed pipeline)")
+    if batch < 2:
+        raise ValueError(f"input_mix: a sample's partner is another sample of its batch (batch >= 2), got {batch}")
+    assert n >= batch and y.shape[0] == batch and tuple(y.shape[1:3]) == (h, w)
+    assert labels.dtype == torch.uint8 and labels.numel() >= n and lab_out.numel() >= batch
+    assert params_out.dtype == torch.int32 and params_out.numel() == 4 * batch and params_out.is_contiguous()
+    assert mix_out.dtype == torch.int32 and mix_out.numel() == 8 * batch and mix_out.is_contiguous()
+    assert table.dtype == torch.int32 and tuple(table.shape) == (2, A.MIX_L) and table.is_contiguous()
+    assert table.device == x_u8.device and cursor.dtype == torch.int32
+    modes = (A.MODE_MIXUP if mixup else 0) | (A.MODE_CUTMIX if cutmix else 0)
+    N.call("sl_input_mix", p(x_u8), p(labels), p(cursor), n, batch, h, w, pad, A.flags(shuffle, augment),
+           seed & ((1 << 64) - 1), p(table), modes, _bf16(y), p(lab_out), p(params_out), p(mix_out),
+           *[float(v) for v in mean], *[float(v) for v in std], N.stream_ptr())
+
+
 def cursor_bump(cursor):
     N.call("sl_cursor_bump", p(cursor), N.stream_ptr())
 
@@ -467,3 +498,20 @@ def softmax_ce(logits, labels, loss, correct, dlogits, dbias, grad_scale):
     n, ncls = logits.shape
     N.call("sl_softmax_ce", _f32(logits), p(labels), _f32(loss), _f32(correct), _bf16(dlogits), dlogits.shape[-1],
            _f32(dbias), n, ncls, float(grad_scale), N.stream_ptr())
+
+
+def softmax_ce_soft(logits, labels, loss, correct, dlogits, dbias, grad_scale, mix=None, eps: float = 0.0):
+    """:func:`softmax_ce` against soft targets (data/augment.py ``soft_targets``): row i's target is
+    ``(1 - eps)(wa [c = la] + wb [c = lb]) + eps / ncls`` with ``la = labels[i]`` and, from row i of
+    ``mix`` (int32 [n, 8], :func:`input_mix`'s ``mix_out``; None = label smoothing alone),
+    ``lb = labels[mix[i, 0]]``, ``wb = mix[i, 1] / mix[i, 2]``, ``wa = 1 - wb``.  ``correct`` stays the
+    argmax against ``la``: under mixing it is a diagnostic, not an accuracy."""
+    n, ncls = logits.shape
+    if not 0 <= eps < 1:
+        raise ValueError(f"label smoothing must be in [0, 1), got {eps!r}")
+    assert labels.dtype == torch.uint8 and labels.numel() >= n
+    if mix is not None:
+        assert mix.dtype == torch.int32 and mix.numel() == 8 * n and mix.is_contiguous()
+    N.call("sl_softmax_ce_soft", _f32(logits), p(labels), _f32(loss), _f32(correct), _bf16(dlogits),
+           dlogits.shape[-1], _f32(dbias), n, ncls, float(grad_scale), p(mix) if mix is not None else None,
+           float(eps), N.stream_ptr())

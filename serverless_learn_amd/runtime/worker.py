@@ -156,6 +156,9 @@ class Worker:
         if (c.augment, c.augment_pad, c.shuffle) != ("none", 4, False):
             # (an unknown name or a bad pad is refused by the trainer, data/augment.py check)
             kw.update(augment=c.augment, augment_pad=c.augment_pad, shuffle=c.shuffle)
+        if (c.label_smoothing, c.mixup_alpha, c.cutmix_alpha) != (0, 0, 0):
+            # (a mix with batch < 2 is refused by the trainer, data/augment.py check_mix)
+            kw.update(label_smoothing=c.label_smoothing, mixup_alpha=c.mixup_alpha, cutmix_alpha=c.cutmix_alpha)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
