@@ -1,4 +1,5 @@
-// Memory-bound helper kernels: gossip delta-apply (K7), flat fused SGD (K5) and gradient clipping.
+// Memory-bound helper kernels: gossip delta-apply (K7), flat fused SGD (K5), gradient clipping and
+// gradient accumulation.
 #include "common.h"
 
 using namespace sl;
@@ -245,6 +246,41 @@ __global__ __launch_bounds__(CLIP_WG) void clip_scale_kernel(float* __restrict__
   }
 }
 
+// K5d -- gradient accumulation: dst[i] = add ? dst[i] + src[i] : src[i] over two fp32 ranges that
+// do not overlap.  One rounding per element, no atomics, no state: the same bits in both builds.
+// The ranges need only 4-byte alignment (the ResNet engine folds grad[lo:hi] bucket views whose lo
+// is a tensor boundary of the flat layout): `head` elements (< 4, from the launcher) bring dst to
+// a 16-byte boundary and are done one per thread, as is the tail past the last whole float4; the
+// body moves 16 bytes per lane on the dst side and, where src shares dst's misalignment (SRC16,
+// every caller in the engines), on the src side too -- dword loads otherwise.
+template <bool SRC16>
+__global__ __launch_bounds__(256) void accum_flat_kernel(float* __restrict__ dst, const float* __restrict__ src,
+                                                         long n, int head, int add) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long body = (n - head) >> 2;  // whole float4s after the head
+  const long tail0 = head + 4 * body;
+  if (tid < head + (n - tail0)) {  // at most 6 threads of workgroup 0
+    const long i = tid < head ? tid : tail0 + (tid - head);
+    dst[i] = add ? dst[i] + src[i] : src[i];
+  }
+  float* d = dst + head;
+  const float* s = src + head;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long q = tid; q < body; q += stride) {
+    float4 sv;
+    if constexpr (SRC16) {
+      sv = *reinterpret_cast<const float4*>(s + 4 * q);
+    } else {
+      sv = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+    }
+    if (add) {
+      const float4 dv = *reinterpret_cast<const float4*>(d + 4 * q);
+      sv.x = dv.x + sv.x; sv.y = dv.y + sv.y; sv.z = dv.z + sv.z; sv.w = dv.w + sv.w;
+    }
+    *reinterpret_cast<float4*>(d + 4 * q) = sv;
+  }
+}
+
 // f32 -> bf16 copy (shadow refresh after load / broadcast).
 __global__ __launch_bounds__(256) void to_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, long n) {
   const long stride = (long)gridDim.x * blockDim.x;
@@ -336,6 +372,23 @@ int sl_clip_grad_norm(float* g, long n, float max_norm, double* partials, int n_
   hipLaunchKernelGGL(clip_sumsq_kernel, dim3(blocks), dim3(CLIP_WG), 0, stream, g, n, partials);
   SL_CHECK_LAUNCH();
   hipLaunchKernelGGL(clip_scale_kernel, dim3(blocks), dim3(CLIP_WG), 0, stream, g, n, max_norm, partials, norm_out);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// dst[0, n) = add ? dst + src : src for two ranges that do not overlap (the caller's contract),
+// each 4-byte aligned.  The grid depends on n alone.
+int sl_accum_flat(float* dst, const float* src, long n, int add, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!dst || !src || (((uintptr_t)dst | (uintptr_t)src) & 3)) return -1;
+  long head = (long)((16 - ((uintptr_t)dst & 15)) & 15) / 4;  // floats before dst's next 16-byte boundary
+  if (head > n) head = n;
+  const dim3 grid(grid_for(n, 4)), wg(256);
+  if (((uintptr_t)(src + head) & 15) == 0) {
+    hipLaunchKernelGGL(accum_flat_kernel<true>, grid, wg, 0, stream, dst, src, n, (int)head, add);
+  } else {
+    hipLaunchKernelGGL(accum_flat_kernel<false>, grid, wg, 0, stream, dst, src, n, (int)head, add);
+  }
   SL_CHECK_LAUNCH();
   return 0;
 }

@@ -68,6 +68,9 @@ class Config:
     lr_decay_steps: int = 0            # step at which the decay ends (0 = max_steps)
     lr_min_ratio: float = 0.0          # the decay ends at lr_min_ratio * lr
     clip_grad_norm: float = 0.0        # clip the aggregated gradient to this global L2 norm (0 = off, inf = measure)
+    accum_steps: int = 1               # micro-batches per optimizer step (one exchange, one clip, one update)
+    global_batch: int = 0              # > 0: accum_steps is chosen at every membership change so that
+                                       # accum_steps * batch * world is as close to this as it can be (0 = off)
     augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip, data/augment.py)
     augment_pad: int = 4               # crop-flip: black pixels of padding around the image the crop is taken from
     shuffle: bool = False              # resnet18: draw each epoch's records through a fresh permutation of the shard
@@ -102,8 +105,18 @@ class Config:
         self.validate()
 
     def validate(self) -> None:
-        """Refuse combinations no component implements (the input pipeline's, the soft-target loss's
-        and the top-k sparse gossip's)."""
+        """Refuse combinations no component implements (gradient accumulation's, the input pipeline's,
+        the soft-target loss's and the top-k sparse gossip's)."""
+        if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
+            raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
+        if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:
+            raise ValueError(f"global_batch must be an integer >= 0 (0 = off), got {self.global_batch!r}")
+        if self.global_batch > 0 and self.accum_steps != 1:
+            raise ValueError("accum_steps and global_batch: set one of them (global_batch chooses accum_steps)")
+        if 0 < self.global_batch < self.batch:
+            raise ValueError(f"global_batch {self.global_batch} is smaller than one worker's batch {self.batch}")
+        if (self.accum_steps != 1 or self.global_batch > 0) and self.model == "simulate":
+            raise ValueError("accum_steps / global_batch: the simulate model has no gradient to accumulate")
         if (self.augment, self.augment_pad, self.shuffle) != ("none", 4, False) and self.model in ("mlp", "simulate"):
             # the MLP kernels read X from bricks tiled once per shard: a per-sample gather would undo that
             raise ValueError(f"augment / shuffle: the {self.model} model has no input pipeline (model='resnet18')")
@@ -126,6 +139,16 @@ class Config:
             raise ValueError("gossip_topk: the simulate model is growable and is never sparse")
         if self.gossip_compat:
             raise ValueError("gossip_topk: gossip_compat reproduces the reference's dense exchange byte for byte")
+
+    def accum_for(self, world: int) -> int:
+        """Micro-batches per step in a lock-step group of ``world`` workers: ``accum_steps``, or with
+        a ``global_batch`` G the K whose ``K * batch * world`` is nearest to G, ``max(1, floor(G /
+        (batch * world) + 1/2))``.  Every member derives it from the same view, so a group agrees
+        without a collective."""
+        if self.global_batch <= 0:
+            return self.accum_steps
+        per = self.batch * max(1, int(world))
+        return max(1, (2 * self.global_batch + per) // (2 * per))  # floor(G / per + 1/2), in integers
 
     def gossip_k(self, n: int) -> int:
         """Entries per sparse message for an n-parameter model (0 = dense)."""

@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 # (the rules' semantics live there)
-from ..ops.optim import OptSpec, adamw_update, clip_grad_, lr_at, sgd_update  # noqa: F401
+from ..ops.optim import OptSpec, adamw_update, check_accum_steps, clip_grad_, lr_at, sgd_update  # noqa: F401
 from ..utils.graphs import GraphSlots
 
 D_IN = 784
@@ -203,6 +203,35 @@ class OptStateCPU:
             if t is not None:
                 t.zero_()
 
+    # ---- gradient accumulation: the definition the GPU engines are tested against ----
+    accum_steps = 1
+    grad = None  # the aggregated gradient of the last step, as the optimizer took it
+
+    def set_accum(self, k) -> None:
+        """``k`` micro-batches per optimizer step (one exchange, one clip, one update)."""
+        self.accum_steps = check_accum_steps(k)
+
+    @property
+    def samples_per_step(self) -> int:
+        return self.batch * self.accum_steps
+
+    @property
+    def grad_scale(self) -> float:
+        """The gradient is a mean over the global batch ``batch * world_size * accum_steps``."""
+        return 1.0 / (self.batch * self.world_size * self.accum_steps)
+
+    def _accumulate(self, micro) -> tuple:
+        """(loss_sum, correct_sum, g) of one step: ``micro()`` returns them for the micro-batch at
+        ``self.cursor``, already scaled by :attr:`grad_scale`; the cursor is bumped between them
+        (the step bumps it after the last, with the update), and the micro-gradients are summed in
+        fp32 in order, ``((g_0 + g_1) + g_2) + ...``."""
+        loss, correct, g = micro()
+        for _ in range(1, self.accum_steps):
+            self.cursor += 1
+            li, ci, gi = micro()
+            loss, correct, g = loss + li, correct + ci, g + gi
+        return loss, correct, g
+
 
 @dataclass
 class StepStats:
@@ -210,16 +239,22 @@ class StepStats:
     accuracy: float
     samples: int
 
+    @property
+    def n(self) -> int:
+        """Samples behind ``loss`` / ``accuracy`` (a training step's: ``accum_steps * batch``)."""
+        return self.samples
+
 
 class CPUTrainer(OptStateCPU):
     """Plain-torch trainer with the same interface as FusedMLPTrainer (CPU workers)."""
 
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 0.0, seed: int = 0, world_size: int = 1,
-                 flat: torch.Tensor | None = None, **opt):
+                 flat: torch.Tensor | None = None, accum_steps: int = 1, **opt):
         self.batch = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
+        self.set_accum(accum_steps)
         self.params = (flat if flat is not None else init_params(seed)).clone().float()
         self._init_opt(opt)  # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (OptSpec)
         self.cursor = 0
@@ -247,15 +282,19 @@ class CPUTrainer(OptStateCPU):
         self.x, self.y = x_u8.reshape(-1, D_IN), y_u8.reshape(-1)
         self.n_batches = self.x.shape[0] // self.batch
 
-    def step(self) -> None:
+    def _micro(self) -> tuple:
         b = self.cursor % self.n_batches
         xs = self.x[b * self.batch:(b + 1) * self.batch]
         ys = self.y[b * self.batch:(b + 1) * self.batch]
-        loss, correct, g = reference_grads(self.params, xs, ys, 1.0 / (self.batch * self.world_size))
+        return reference_grads(self.params, xs, ys, self.grad_scale)
+
+    def step(self) -> None:
+        loss, correct, g = self._accumulate(self._micro)
         self.phases.mark("compute")
         if self.allreduce is not None:
             self.allreduce(g)
         self.phases.mark("exchange")
+        self.grad = g
         self._opt_update(g)
         self.cursor += 1
         self.phases.mark("update")
@@ -272,7 +311,8 @@ class CPUTrainer(OptStateCPU):
 
     def stats(self) -> StepStats:
         loss, correct = self._last
-        return StepStats(loss / self.batch, correct / self.batch, self.batch)
+        n = self.samples_per_step
+        return StepStats(loss / n, correct / n, n)
 
     def get_flat(self) -> torch.Tensor:
         return self.params.clone()
@@ -290,6 +330,9 @@ class CPUTrainer(OptStateCPU):
 
     def buffers(self) -> list:
         return self._opt_buffers()
+
+
+CPUMLPTrainer = CPUTrainer  # (beside CPUResNetTrainer)
 
 
 def dh1_scale(grad_scale: float) -> float:
@@ -322,7 +365,7 @@ class FusedMLPTrainer(GraphSlots):
 
     def __init__(self, batch: int, device="cuda", lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 0.0, seed: int = 0, world_size: int = 1,
-                 slices: int | None = None, flat: torch.Tensor | None = None, **opt):
+                 slices: int | None = None, flat: torch.Tensor | None = None, accum_steps: int = 1, **opt):
         from ..ops import _native
 
         if batch % BLOCK_ROWS != 0:
@@ -336,7 +379,9 @@ class FusedMLPTrainer(GraphSlots):
         self.batch = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
-        self.grad_scale = 1.0 / (batch * world_size)
+        # accum_steps micro-batches per optimizer step: the gradient stays a mean over all of them
+        self.accum_steps = check_accum_steps(accum_steps)
+        self.grad_scale = 1.0 / (batch * world_size * self.accum_steps)
         s1 = slices or int(os.environ.get("SL_MLP_WG_SLICES", "0") or 0)  # split-K slices (0: library default)
         self.slices = int(_native.lib().sl_mlp_wgrad_slices(batch, s1))
         if self.slices <= 0:
@@ -387,6 +432,9 @@ class FusedMLPTrainer(GraphSlots):
         self.slab_stride = int(lib.sl_mlp_slab_stride()) if hasattr(lib, "sl_mlp_slab_stride") else self.n_pad
         self.slab = torch.empty(self.slices, self.slab_stride, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)
+        # gradient accumulation's partial sums (gradient, per-sample loss and correct): None at accum_steps 1
+        self.acc = self.loss_acc = self.correct_acc = None
+        self._alloc_accum()
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.allreduce = None  # callable(grad_tensor) -> None, sums in place (RCCL)
         self.xgmi = None       # parallel.xgmi.XgmiExchange: all-reduce fused into the update (no RCCL)
@@ -411,8 +459,37 @@ class FusedMLPTrainer(GraphSlots):
     def set_world(self, world: int) -> None:
         """Gradient scale follows the group size (mean over the global batch)."""
         self.world_size = world
-        self.grad_scale = 1.0 / (self.batch * world)
+        self.grad_scale = 1.0 / (self.batch * world * self.accum_steps)
         self.graph = None
+
+    def _alloc_accum(self) -> None:
+        if self.accum_steps == 1:
+            self.acc = self.loss_acc = self.correct_acc = None
+        elif self.acc is None:
+            from ..ops.optim import ACCUM_KERNELS, require_kernels
+
+            require_kernels(self.opt, *ACCUM_KERNELS, "sl_cursor_bump")
+            self.acc = torch.zeros_like(self.grad)
+            self.loss_acc, self.correct_acc = torch.zeros_like(self.loss), torch.zeros_like(self.correct)
+
+    def set_accum(self, k: int) -> None:
+        """``k`` micro-batches per optimizer step: each runs rows / wgrad / reduce on its own batch
+        (the cursor moves after each), the reduced gradients are summed in fp32 in order, and the
+        sum takes the exchange hook, the clip and one update.  The gradient scale follows (a mean
+        over ``k * batch * world``); the launches are rebuilt and the captured graphs dropped.
+        Not with the xGMI exchange, which reduces the slab straight into its slot."""
+        k = check_accum_steps(k)
+        if k > 1 and self.xgmi is not None:
+            raise ValueError("gradient accumulation is not available with the xGMI exchange "
+                             "(keep the process group's all-reduce)")
+        self.accum_steps = k
+        self._alloc_accum()
+        self.set_world(self.world_size)
+        self.graph_unrolled = None
+
+    @property
+    def samples_per_step(self) -> int:
+        return self.batch * self.accum_steps
 
     # ---- data ----
     def load_shard(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> None:
@@ -493,7 +570,7 @@ class FusedMLPTrainer(GraphSlots):
                self.n_batches, self.grad_scale, self.lr,
                self.momentum, self.weight_decay, id(self.xgmi), bool(self.xgmi and self.xgmi.two_shot),
                self.xgmi.inline_sync if self.xgmi is not None else None, None if self.opt.plain else self.opt,
-               self.opt.clip_grad_norm)
+               self.opt.clip_grad_norm, self.accum_steps)
         if getattr(self, "_lkey", None) == key:
             return self._lc
         n, p = self._n, self._n.ptr
@@ -531,6 +608,16 @@ class FusedMLPTrainer(GraphSlots):
         if self.opt.clips:  # between the reduce and the update launches, on the real parameters only
             lc["clip"] = n.Launch("sl_clip_grad_norm", p(self.grad), N_PARAMS, self.opt.clip_grad_norm,
                                   p(self.clip_partials), self.clip_partials.numel(), p(self.clip_norm))
+        if self.accum_steps > 1:
+            # the sums of an accumulated step: store after micro-batch 0, add after 1 .. K-2, and the
+            # fold of the partial sums into grad / loss / correct after the last; the earlier
+            # micro-batches' cursor bump (the update launch bumps it after the last)
+            pairs = ((self.acc, self.grad, N_PARAMS), (self.loss_acc, self.loss, self.batch),
+                     (self.correct_acc, self.correct, self.batch))
+            for name, add in (("acc_store", 0), ("acc_add", 1)):
+                lc[name] = [n.Launch("sl_accum_flat", p(a), p(t), cnt, add) for a, t, cnt in pairs]
+            lc["acc_fold"] = [n.Launch("sl_accum_flat", p(t), p(a), cnt, 1) for a, t, cnt in pairs]
+            lc["bump"] = n.Launch("sl_cursor_bump", p(self.cursor))
         if self.xgmi is not None:
             xg = self.xgmi
             # inline synchronisation: the reduce publishes the step, the update waits per workgroup
@@ -608,6 +695,9 @@ class FusedMLPTrainer(GraphSlots):
         if exchange is not None and self.opt.clips:
             raise ValueError("gradient clipping is not available with the xGMI exchange "
                              "(keep the process-group all-reduce)")
+        if exchange is not None and self.accum_steps > 1:
+            raise ValueError("gradient accumulation is not available with the xGMI exchange "
+                             "(keep the process-group all-reduce)")
         if exchange is not None and exchange.payload_floats < self.n_pad:
             raise ValueError("exchange slot smaller than the parameter vector")
         self.xgmi = exchange
@@ -641,6 +731,8 @@ class FusedMLPTrainer(GraphSlots):
         if getattr(self, "probe", None) is not None:
             self.probe()
         ph = self.phases
+        if self.accum_steps > 1:
+            return self._step_accum()
         self._rows(True)
         self._wgrad()
         ph.mark("compute")
@@ -661,6 +753,27 @@ class FusedMLPTrainer(GraphSlots):
             if self.opt.clips:  # the whole norm before any weight moves: the fused slab update cannot clip
                 self._launches()["clip"]()
             self._sgd(2, from_grad=True, grad_out=False)
+        ph.mark("update")
+
+    def _step_accum(self) -> None:
+        """One step of ``accum_steps`` micro-batches: grad = ((g_0 + g_1) + ...) + g_last, then the
+        reduce -> hook -> clip -> update path of a clipping step (no fused slab update)."""
+        lc, ph, last = self._launches(), self.phases, self.accum_steps - 1
+        for i in range(last + 1):
+            lc["rows"]()
+            lc["wgrad"]()
+            lc["reduce"]()
+            for launch in lc["acc_fold" if i == last else "acc_add" if i else "acc_store"]:
+                launch()
+            if i < last:
+                lc["bump"]()
+        ph.mark("compute")
+        if self.allreduce is not None:
+            self.allreduce(self.grad)
+            ph.mark("exchange")
+        if self.opt.clips:
+            lc["clip"]()
+        lc["update"]()
         ph.mark("update")
 
     def grad_norm(self) -> float | None:
@@ -723,7 +836,8 @@ class FusedMLPTrainer(GraphSlots):
         acc = float(self.correct.sum())
         if self.w1_out_of_range():
             loss = float("nan")  # visible: never a number from a saturated layer 1
-        return StepStats(loss / self.batch, acc / self.batch, self.batch)
+        n = self.samples_per_step  # (an accumulated step leaves the sums over its micro-batches in loss / correct)
+        return StepStats(loss / n, acc / n, n)
 
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> StepStats:
         n = self._n

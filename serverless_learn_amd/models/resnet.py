@@ -253,7 +253,8 @@ class CPUResNetTrainer(OptStateCPU):
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 5e-4,
                  seed: int = 0, world_size: int = 1, stem: str = "cifar", flat: torch.Tensor | None = None,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
-                 label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, **opt):
+                 label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
+                 accum_steps: int = 1, **opt):
         from ..data import augment as A
         from .mlp import StepStats, sgd_update  # noqa: F401
 
@@ -272,6 +273,7 @@ class CPUResNetTrainer(OptStateCPU):
         self.batch = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
+        self.set_accum(accum_steps)
         self.params = (flat if flat is not None else init_params(self.spec, seed)).clone().float()
         self._init_opt(opt)  # optimizer=, beta1=, ..., lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
         self.running = running_stats(self.spec)
@@ -306,7 +308,9 @@ class CPUResNetTrainer(OptStateCPU):
         self.y = y_u8.reshape(-1)
         self.n_batches = self.x.shape[0] // self.batch
 
-    def step(self) -> None:
+    def _micro(self) -> tuple:
+        """(loss_sum, correct_sum, g) of the micro-batch at the cursor (BatchNorm: its own batch
+        statistics, and one update of the running statistics)."""
         from ..data import augment as A
 
         mixes = self.mixup_alpha > 0 or self.cutmix_alpha > 0
@@ -328,12 +332,15 @@ class CPUResNetTrainer(OptStateCPU):
         if mixes or self.label_smoothing > 0:
             targets = torch.from_numpy(A.soft_targets(ys.cpu().numpy(), self.last_mix, self.label_smoothing,
                                                       self.spec.classes))
-        loss, correct, g = ref_grads(self.spec, self.params, xs, ys, 1.0 / (self.batch * self.world_size),
-                                     self.running, targets)
+        return ref_grads(self.spec, self.params, xs, ys, self.grad_scale, self.running, targets)
+
+    def step(self) -> None:
+        loss, correct, g = self._accumulate(self._micro)
         self.phases.mark("compute")
         if self.allreduce is not None:
             self.allreduce(g)
         self.phases.mark("exchange")
+        self.grad = g
         self._opt_update(g)
         self.cursor += 1
         self.phases.mark("update")
@@ -352,7 +359,8 @@ class CPUResNetTrainer(OptStateCPU):
         from .mlp import StepStats
 
         loss, correct = self._last
-        return StepStats(loss / self.batch, correct / self.batch, self.batch)
+        n = self.samples_per_step
+        return StepStats(loss / n, correct / n, n)
 
     def get_flat(self) -> torch.Tensor:
         return self.params.clone()

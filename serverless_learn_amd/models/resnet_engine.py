@@ -82,7 +82,8 @@ class FusedResNetTrainer(GraphSlots):
                  weight_decay: float = 5e-4, seed: int = 0, world_size: int = 1, stem: str = "cifar",
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
-                 label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, **opt):
+                 label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
+                 accum_steps: int = 1, **opt):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
@@ -103,7 +104,9 @@ class FusedResNetTrainer(GraphSlots):
         self.batch = B = batch
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.world_size = world_size
-        self.grad_scale = 1.0 / (batch * world_size)
+        # accum_steps micro-batches per optimizer step: the gradient stays a mean over all of them
+        self.accum_steps = O.check_accum_steps(accum_steps)
+        self.grad_scale = 1.0 / (batch * world_size * self.accum_steps)
         self.bn_momentum = bn_momentum
         self.shortcut_even_on = os.environ.get("SL_SHORTCUT_EVEN", "1") != "0"
         # BN-on-load: where the direct 3x3 kernel serves a block's conv2 (64 channels, 32 wide), it
@@ -212,6 +215,9 @@ class FusedResNetTrainer(GraphSlots):
         self.dlogits = torch.zeros(B, 1, 1, LOGIT_LD, **bf)
         self.loss = torch.zeros(B, device=dev)
         self.correct = torch.zeros(B, device=dev)
+        # gradient accumulation's partial sums (gradient, per-sample loss and correct): None at accum_steps 1
+        self.acc = self.loss_acc = self.correct_acc = None
+        self._alloc_accum()
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.x = self.y = None
         self.graph = None
@@ -262,8 +268,30 @@ class FusedResNetTrainer(GraphSlots):
 
     def set_world(self, world: int) -> None:
         self.world_size = world
-        self.grad_scale = 1.0 / (self.batch * world)
+        self.grad_scale = 1.0 / (self.batch * world * self.accum_steps)
         self.graph = None
+
+    def _alloc_accum(self) -> None:
+        if self.accum_steps == 1:
+            self.acc = self.loss_acc = self.correct_acc = None
+        elif self.acc is None:
+            self.O.require_kernels(self.opt, *self.O.ACCUM_KERNELS)
+            self.acc = torch.zeros_like(self.grad)
+            self.loss_acc, self.correct_acc = torch.zeros_like(self.loss), torch.zeros_like(self.correct)
+
+    def set_accum(self, k: int) -> None:
+        """``k`` micro-batches per optimizer step: each runs forward and backward on its own batch
+        (own input-pipeline draws, own BatchNorm statistics; the cursor moves after each), the
+        gradients are summed in fp32 in order, and the sum takes the bucket hooks / all-reduce,
+        the clip and one update.  The gradient scale follows (a mean over ``k * batch * world``)
+        and the captured graph is dropped."""
+        self.accum_steps = self.O.check_accum_steps(k)
+        self._alloc_accum()
+        self.set_world(self.world_size)
+
+    @property
+    def samples_per_step(self) -> int:
+        return self.batch * self.accum_steps
 
     # ------------------------------------------------------------------
     def refresh_shadows(self) -> None:
@@ -347,7 +375,10 @@ class FusedResNetTrainer(GraphSlots):
             K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
                          self.fc_gb if train else None, self.grad_scale)
 
-    def backward(self):
+    def backward(self, hook: bool = True, fold: bool = False):
+        """``hook=False``: no bucket hook is called (an accumulated step's earlier micro-batches).
+        ``fold``: the partial sum ``acc`` of the earlier micro-batches is added into each bucket's
+        range of ``grad`` just before the hook takes it (the last micro-batch)."""
         K, spec = self.K, self.spec
         handles = []
         pending_from = spec.n_flat  # grad[pending_from:] is final and not yet reduced
@@ -359,11 +390,13 @@ class FusedResNetTrainer(GraphSlots):
 
         def maybe_bucket(lo, force=False):
             nonlocal pending_from
-            if self.bucket_hook is None:
+            if self.bucket_hook is None or not hook:
                 return
             if force or (pending_from - lo) >= bucket_elems:
                 if side is not None:
                     K.wgrad_side_join(end=False)  # the bucket's reduces are in the gradient
+                if fold:
+                    self.O.accum_flat(self.grad[lo:pending_from], self.acc[lo:pending_from], True)
                 handles.append(self.bucket_hook(self.grad[lo:pending_from]))
                 pending_from = lo
 
@@ -461,12 +494,32 @@ class FusedResNetTrainer(GraphSlots):
             K.wgrad_side_join(end=True)
         return handles
 
+    def _accum_sums(self, i: int) -> None:
+        """After micro-batch ``i`` of an accumulated step: its gradient, per-sample loss and correct
+        into the partial sums (stored after the first, added after the others)."""
+        for a, t in ((self.acc, self.grad), (self.loss_acc, self.loss), (self.correct_acc, self.correct)):
+            self.O.accum_flat(a, t, i > 0)
+
     def _step_eager(self) -> None:
         self.grad.zero_()
         if not torch.cuda.is_current_stream_capturing():
             self.wgws.grow()  # size the split-K slab before any capture (first call: atomics)
+        last = self.accum_steps - 1
+        for i in range(last):  # an accumulated step's earlier micro-batches: no exchange
+            self.forward(train=True)
+            self.backward(hook=False)
+            self._accum_sums(i)
+            self.K.cursor_bump(self.cursor)
+            self.grad.zero_()
         self.forward(train=True)
-        handles = self.backward()
+        # grad = ((g_0 + g_1) + ...) + g_last: bucket by bucket ahead of each hook, so the bucket
+        # all-reduces still overlap the rest of this backward; in one launch with no bucket hook
+        handles = self.backward(fold=last > 0)
+        if last > 0:
+            if self.bucket_hook is None:
+                self.O.accum_flat(self.grad, self.acc, True)
+            self.O.accum_flat(self.loss, self.loss_acc, True)
+            self.O.accum_flat(self.correct, self.correct_acc, True)
         self.phases.mark("compute")
         if self.bucket_wait is not None:
             self.bucket_wait(handles)  # the bucket all-reduces ran during backward: the exposed part
@@ -546,7 +599,8 @@ class FusedResNetTrainer(GraphSlots):
         return self.grad
 
     def stats(self) -> StepStats:
-        return StepStats(float(self.loss.sum()) / self.batch, float(self.correct.sum()) / self.batch, self.batch)
+        n = self.samples_per_step  # (an accumulated step leaves the sums over its micro-batches in loss / correct)
+        return StepStats(float(self.loss.sum()) / n, float(self.correct.sum()) / n, n)
 
     def get_flat(self) -> torch.Tensor:
         return self.params.clone()

@@ -11,6 +11,9 @@ learning rate; the schedule reaches the kernels as an fp32 table of ``lr_at`` va
 Either rule may be preceded by global-norm gradient clipping (``clip_grad_norm``,
 ``torch.nn.utils.clip_grad_norm_``): :func:`clip_grad_` is its reference, and
 :func:`clip_grad_norm_flat` the two-launch kernel that a captured graph replays.
+
+Gradient accumulation (``accum_steps`` micro-batches per update) sums the micro-gradients ahead of
+all that with :func:`accum_flat`, one fp32 add per element in a fixed order.
 """
 from __future__ import annotations
 
@@ -36,6 +39,8 @@ N.register("sl_sgd_flat_lr", [N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, 
 _STEP = [N.P, N.P, N.P, N.I]  # step, ticket, lr table, its length
 N.register("sl_clip_grad_partials", [N.L])
 N.register("sl_clip_grad_norm", [N.P, N.L, N.F, N.P, N.I, N.P, N.P])
+N.register("sl_accum_flat", [N.P, N.P, N.L, N.I, N.P])
+N.register("sl_cursor_bump", [N.P, N.P])  # (ops/cnn.py's launcher: the MLP's accumulated step bumps its cursor with it)
 N.register("sl_mlp_opt", [N.I, N.P, N.P, N.P, N.P, N.I, N.L, N.P, N.F, N.F, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P,
                           N.P, N.P, *_STEP, *_ADAM, N.P])
 N.register("sl_mlp_opt_xgmi", [N.I, N.P, N.P, N.P, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.L, N.I,
@@ -191,13 +196,15 @@ class OptSpec:
 
 
 def require_kernels(spec: OptSpec, *names: str) -> None:
-    """The step-counter rules and gradient clipping need their entry points: an older kernel
-    build (kept for A/B runs of the SGD path) does not have them, and there is no fallback."""
+    """The step-counter rules, gradient clipping and gradient accumulation need their entry
+    points: an older kernel build (kept for A/B runs of the SGD path) does not have them, and
+    there is no fallback."""
     lib = N.lib()
     missing = [n for n in names if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"optimizer {spec.optimizer!r} / lr_schedule {spec.lr_schedule!r} / clip_grad_norm "
-                           f"{spec.clip_grad_norm!r} need {', '.join(missing)}: not in this kernel library")
+                           f"{spec.clip_grad_norm!r} / accum_steps > 1 need {', '.join(missing)}: not in this "
+                           "kernel library")
 
 
 # ---- flat kernels ----
@@ -263,3 +270,26 @@ def clip_grad_norm_flat(g: torch.Tensor, max_norm: float, partials: torch.Tensor
     assert partials.dtype == torch.float64 and partials.is_contiguous() and norm_out.dtype == torch.float32
     N.call("sl_clip_grad_norm", N.ptr(g), g.numel(), float(max_norm), N.ptr(partials), partials.numel(),
            N.ptr(norm_out), N.stream_ptr())
+
+
+ACCUM_KERNELS = ("sl_accum_flat",)
+
+
+def check_accum_steps(k) -> int:
+    """``accum_steps`` of a trainer: an integer >= 1."""
+    if isinstance(k, bool) or int(k) != k or int(k) < 1:
+        raise ValueError(f"accum_steps must be an integer >= 1, got {k!r}")
+    return int(k)
+
+
+def accum_flat(dst: torch.Tensor, src: torch.Tensor, add) -> None:
+    """Gradient accumulation's one launch (csrc/kernels/elementwise.hip): ``dst = dst + src``
+    (``add``) or ``dst = src``, elementwise in fp32, one rounding per element and no atomics, so
+    the bits are the same from call to call and in both kernel builds.  ``dst`` and ``src`` are
+    contiguous fp32 ranges of one length that do not overlap; any 4-byte alignment will do (views
+    ``grad[lo:hi]`` of the flat vector)."""
+    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.float32 and src.dtype == torch.float32
+    assert dst.is_contiguous() and src.is_contiguous() and dst.numel() == src.numel()
+    nbytes, a, b = 4 * dst.numel(), dst.data_ptr(), src.data_ptr()
+    assert a + nbytes <= b or b + nbytes <= a, "accum_flat: dst and src overlap"
+    N.call("sl_accum_flat", a, b, dst.numel(), int(bool(add)), N.stream_ptr())

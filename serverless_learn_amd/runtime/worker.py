@@ -91,7 +91,7 @@ class Worker:
         self.view = {"epoch": 0, "peers": [], "rank": -1, "world": 0, "rendezvous": "", "resume_file": 0}
         self.trainer = None
         self.xgmi = None  # parallel.xgmi.XgmiExchange while an RCCL group of MLP workers is live
-        self._xgmi_skip_logged = False  # one xgmi_skipped event per worker (gradient clipping)
+        self._xgmi_skip_logged = False  # one xgmi_skipped event per worker (gradient clipping / accumulation)
         self.gossip: GossipState | None = None
         backend = None if self.cfg.dp_backend == "auto" else self.cfg.dp_backend
         timeout = float(self.cfg.extra.get("dp_timeout_s", self.cfg.dp_timeout_s))
@@ -159,6 +159,8 @@ class Worker:
         if (c.label_smoothing, c.mixup_alpha, c.cutmix_alpha) != (0, 0, 0):
             # (a mix with batch < 2 is refused by the trainer, data/augment.py check_mix)
             kw.update(label_smoothing=c.label_smoothing, mixup_alpha=c.mixup_alpha, cutmix_alpha=c.cutmix_alpha)
+        if c.accum_for(world) != 1:  # accum_steps, or the K nearest to global_batch at this world
+            kw.update(accum_steps=c.accum_for(world))
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
@@ -171,9 +173,18 @@ class Worker:
             self.trainer.refresh_shadows()
 
     def _set_world(self, world: int):
-        """Gradient scale follows the group size (mean over the global batch)."""
-        if self.trainer is not None:
-            self.trainer.set_world(world)
+        """Gradient scale follows the group size (mean over the global batch); with a
+        ``global_batch`` target so does the number of micro-batches per step (Config.accum_for)."""
+        t = self.trainer
+        if t is None:
+            return
+        t.set_world(world)
+        if self.cfg.global_batch > 0:
+            k = self.cfg.accum_for(world)
+            if k != getattr(t, "accum_steps", k):  # (a trainer without the knob keeps what it has)
+                t.set_accum(k)  # the gradient scale uses the batch actually reached; the graphs are dropped
+                self.log.info("accum_steps", accum_steps=k, world=world, global_batch=t.samples_per_step * world,
+                              target=self.cfg.global_batch)
 
     # ---- RPC handlers --------------------------------------------------------
     def _receive_file(self, requests, context) -> bytes:
@@ -534,6 +545,14 @@ class Worker:
             return False
         if not (self.group.backend == "nccl" or os.environ.get("SL_XGMI_GLOO", "0") == "1"):
             return False
+        if self.cfg.global_batch > 0 or getattr(t, "accum_steps", 1) > 1:
+            # the fused exchange reduces each micro-batch's slab straight into the exchange slot: there
+            # is no local gradient to accumulate.  The group keeps the process group's all-reduce.
+            if not self._xgmi_skip_logged:
+                self._xgmi_skip_logged = True
+                self.log.info("xgmi_skipped", reason="gradient accumulation needs the local gradient before the "
+                              "exchange", accum_steps=getattr(t, "accum_steps", 1), global_batch=self.cfg.global_batch)
+            return False
         if self.cfg.clip_grad_norm > 0:
             # the fused exchange sums the peers' slots inside the update kernel: there is no summed
             # gradient to clip before it.  The group keeps the process group's all-reduce.
@@ -742,7 +761,7 @@ class Worker:
 
     def _account_steps(self, prev: int, ran: int) -> None:
         self.step = prev + ran
-        self.samples += ran * self.trainer.batch
+        self.samples += ran * self._samples_per_step()
         for s_i in range(prev + 1, self.step + 1):
             self.fault.on_step(s_i)
 
@@ -755,7 +774,7 @@ class Worker:
                                   "accuracy": st.accuracy, "world": 1}
             return
         dev = self.device if self.group.backend == "nccl" else torch.device("cpu")
-        b = float(self.trainer.batch)
+        b = float(self._samples_per_step())  # (accum_steps * batch: what st.loss and st.accuracy are means over)
         v = torch.tensor([st.loss * b, st.accuracy * b, b, float(samples)], dtype=torch.float64, device=dev)
         m = torch.tensor([dt], dtype=torch.float64, device=dev)
         self.group.allreduce_(v)
@@ -887,7 +906,7 @@ class Worker:
                     self._group_metrics_update(dt, self.samples - s_last, st)
                 except GroupBroken as e:
                     self.log.warn("group_metrics_failed", error=str(e))
-                steps_i = max(1, (self.samples - s_last) // max(1, self.trainer.batch))
+                steps_i = max(1, (self.samples - s_last) // max(1, self._samples_per_step()))
                 self.phase_stats["step_ms"] = dt * 1e3 / steps_i
                 self.phase_stats["data_wait_ms"] = self._wait_s * 1e3 / steps_i
                 self._wait_s = 0.0
@@ -906,7 +925,7 @@ class Worker:
                 self.log.info("train", step=self.step, loss=round(st.loss, 4), acc=round(st.accuracy, 4),
                               samples_per_sec=round(self.rate, 1), epoch=self.group.epoch,
                               group_samples_per_sec=round(gm["samples_per_sec"], 1), group_world=gm["world"],
-                              group_loss=round(gm["loss"], 4), graph=self._use_graph(),
+                              group_loss=round(gm["loss"], 4), graph=self._use_graph(), **self._batch_fields(),
                               **{k: round(v, 4) for k, v in self.phase_stats.items()}, **extra)
             if (self.cfg.checkpoint_every and self.step // self.cfg.checkpoint_every != prev // self.cfg.checkpoint_every
                     and (self.group.rank <= 0)):
@@ -917,6 +936,17 @@ class Worker:
             if self.cfg.max_steps and self.step >= self.cfg.max_steps:
                 self.state = "done"
                 return
+
+    def _batch_fields(self) -> dict:
+        """The ``train`` event's ``accum_steps`` and ``global_batch``: the samples behind one update
+        of the whole group, ``accum_steps * batch * world``."""
+        t = self.trainer
+        return {"accum_steps": getattr(t, "accum_steps", 1),
+                "global_batch": self._samples_per_step() * getattr(t, "world_size", 1)}
+
+    def _samples_per_step(self) -> int:
+        """Samples this worker consumes per optimizer step: ``accum_steps * batch``."""
+        return getattr(self.trainer, "samples_per_step", self.trainer.batch)
 
     def _idle(self, secs: float, event: threading.Event | None = None) -> None:
         """A wait of the training loop (no data, waiting for the group or a peer's data):

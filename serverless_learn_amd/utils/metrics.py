@@ -13,6 +13,7 @@ numeric fields of a few well-known events feed gauges / counters / histograms:
 * any ``epoch`` / ``world`` field -> ``sl_membership_epoch`` / ``sl_world_size``
 * ``train``'s step-time breakdown -> ``sl_step_phase_ms{phase}``, ``sl_exchange_gbps``
 * ``train``'s ``grad_norm`` (gradient clipping on) -> ``sl_grad_norm``
+* ``train``'s ``global_batch`` (``accum_steps * batch * world``) -> ``sl_global_batch``
 
 Besides the log events, the transport reports every RPC it serves or makes (SURVEY.md §5.1,
 "per-RPC latency histograms"): ``sl_rpc_seconds{role,side,method,code}`` -- side ``server`` /
@@ -76,6 +77,8 @@ class Metrics:
                                    ["role"], registry=r)
         self.grad_norm = Gauge("sl_grad_norm", "global L2 norm of the last step's aggregated gradient before "
                                "clipping (reported with gradient clipping on)", ["role"], registry=r)
+        self.global_batch = Gauge("sl_global_batch", "samples behind one optimizer step of the whole group "
+                                  "(micro-batches per step x per-worker batch x group size)", ["role"], registry=r)
 
     # ---- fed by the transport ---------------------------------------------------------
     def rpc(self, side: str, method: str, code: str, seconds: float) -> None:
@@ -121,6 +124,8 @@ class Metrics:
                     self.exchange_gbps.labels(role).set(fields["exchange_gbps"])
                 if isinstance(fields.get("grad_norm"), (int, float)):
                     self.grad_norm.labels(role).set(fields["grad_norm"])
+                if isinstance(fields.get("global_batch"), (int, float)):
+                    self.global_batch.labels(role).set(fields["global_batch"])
             elif event == "job":
                 if isinstance(fields.get("samples_per_sec"), (int, float)):
                     self.job_rate.labels(role).set(fields["samples_per_sec"])
