@@ -1,5 +1,5 @@
-// Memory-bound helper kernels: gossip delta-apply (K7), flat fused SGD (K5), gradient clipping and
-// gradient accumulation.
+// Memory-bound helper kernels: gossip delta-apply (K7), flat fused SGD (K5), gradient clipping,
+// gradient accumulation and the weight EMA.
 #include "common.h"
 
 using namespace sl;
@@ -281,6 +281,56 @@ __global__ __launch_bounds__(256) void accum_flat_kernel(float* __restrict__ dst
   }
 }
 
+// K5e -- weight EMA: e <- e + omd * (w - e) over the flat fp32 parameters, after the update launch,
+// with omd = omd_tab[min(*step, tab_last)] (float32(1 - decay_t), from the host).  Three fp32
+// operations, each rounded once and none contracted into an fma, so torch's e + omd * (w - e) gives
+// the same bits (ops/optim.py ema_update_) and w == e is a fixed point.  Same walk as sgd_flat_kernel
+// over two whole allocations; the n % 4 tail is done by the first lanes of workgroup 0.  Every
+// workgroup reads the step once at its start (wave-uniform; the table entry is a scalar load of a
+// kernel-argument pointer at a uniform index) and the launch advances it at its end with the ticket
+// protocol of mlp_fused.hip opt_end: one launch per step, no bump launch, no float atomics.
+// (Plain operators under contract(off), not __fsub_rn / __fmul_rn / __fadd_rn: those are inline
+// functions over the same operators, compiled under the translation unit's fast contraction, and the
+// multiply and the add came out as one v_fma.  The pragma takes the contract flag off these three.)
+__device__ __forceinline__ float ema_one(float e, float w, float omd) {
+#pragma clang fp contract(off)
+  const float d = w - e;
+  const float p = omd * d;
+  return e + p;
+}
+
+__global__ __launch_bounds__(256) void ema_flat_kernel(float* __restrict__ ema, const float* __restrict__ w, long n,
+                                                       int* step, unsigned* ticket,
+                                                       const float* __restrict__ omd_tab, int tab_last) {
+  const int k = __builtin_amdgcn_readfirstlane(__hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const float omd = omd_tab[k < 0 ? 0 : k < tab_last ? k : tab_last];
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long body = n >> 2;  // whole float4s
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long q = tid; q < body; q += stride) {
+    float4 e = *reinterpret_cast<const float4*>(ema + 4 * q);
+    const float4 x = *reinterpret_cast<const float4*>(w + 4 * q);
+    e.x = ema_one(e.x, x.x, omd);
+    e.y = ema_one(e.y, x.y, omd);
+    e.z = ema_one(e.z, x.z, omd);
+    e.w = ema_one(e.w, x.w, omd);
+    *reinterpret_cast<float4*>(ema + 4 * q) = e;
+  }
+  if (tid < (n & 3)) {  // at most 3 lanes of workgroup 0
+    const long i = 4 * body + tid;
+    ema[i] = ema_one(ema[i], w[i], omd);
+  }
+  // every workgroup of this launch has read the step before the last ticket is drawn (opt_end)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t + 1u == gridDim.x) {
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(step, k + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // f32 -> bf16 copy (shadow refresh after load / broadcast).
 __global__ __launch_bounds__(256) void to_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, long n) {
   const long stride = (long)gridDim.x * blockDim.x;
@@ -389,6 +439,21 @@ int sl_accum_flat(float* dst, const float* src, long n, int add, hipStream_t str
   } else {
     hipLaunchKernelGGL(accum_flat_kernel<false>, grid, wg, 0, stream, dst, src, n, (int)head, add);
   }
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// ema[0, n) += omd * (w - ema) with omd = omd_tab[min(*step, tab_n - 1)], then *step += 1, in one
+// launch (ema_flat_kernel).  ema and w are whole 16-byte-aligned allocations that do not overlap;
+// *ticket is 0 between launches.  The grid depends on n alone.
+int sl_ema_flat(float* ema, const float* w, long n, int* step, unsigned* ticket, const float* omd_tab, int tab_n,
+                hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!ema || !w || !step || !ticket || !omd_tab || tab_n < 1) return -1;
+  if (((uintptr_t)ema | (uintptr_t)w) & 15) return -1;
+  if (((uintptr_t)step | (uintptr_t)ticket | (uintptr_t)omd_tab) & 3) return -1;
+  hipLaunchKernelGGL(ema_flat_kernel, dim3(grid_for(n, 4)), dim3(256), 0, stream, ema, w, n, step, ticket, omd_tab,
+                     tab_n - 1);
   SL_CHECK_LAUNCH();
   return 0;
 }

@@ -71,6 +71,9 @@ class Config:
     accum_steps: int = 1               # micro-batches per optimizer step (one exchange, one clip, one update)
     global_batch: int = 0              # > 0: accum_steps is chosen at every membership change so that
                                        # accum_steps * batch * world is as close to this as it can be (0 = off)
+    ema_decay: float = 0.0             # > 0: keep an exponential moving average of the weights, updated after every
+                                       # optimizer step (0 = off; < 1)
+    ema_warmup: bool = True            # decay_t = min(ema_decay, (1 + t) / (10 + t)): early updates weigh more
     augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip, data/augment.py)
     augment_pad: int = 4               # crop-flip: black pixels of padding around the image the crop is taken from
     shuffle: bool = False              # resnet18: draw each epoch's records through a fresh permutation of the shard
@@ -105,8 +108,8 @@ class Config:
         self.validate()
 
     def validate(self) -> None:
-        """Refuse combinations no component implements (gradient accumulation's, the input pipeline's,
-        the soft-target loss's and the top-k sparse gossip's)."""
+        """Refuse combinations no component implements (gradient accumulation's, the weight EMA's,
+        the input pipeline's, the soft-target loss's and the top-k sparse gossip's)."""
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
         if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:
@@ -117,6 +120,12 @@ class Config:
             raise ValueError(f"global_batch {self.global_batch} is smaller than one worker's batch {self.batch}")
         if (self.accum_steps != 1 or self.global_batch > 0) and self.model == "simulate":
             raise ValueError("accum_steps / global_batch: the simulate model has no gradient to accumulate")
+        if self.ema_decay != 0:  # NaN included
+            from .ops.optim import ema_table_len
+
+            ema_table_len(self.ema_decay, self.ema_warmup)  # a bad decay, a warm-up table that is too long
+            if self.model == "simulate":
+                raise ValueError("ema_decay: the simulate model has no trained weights to average")
         if (self.augment, self.augment_pad, self.shuffle) != ("none", 4, False) and self.model in ("mlp", "simulate"):
             # the MLP kernels read X from bricks tiled once per shard: a per-sample gather would undo that
             raise ValueError(f"augment / shuffle: the {self.model} model has no input pipeline (model='resnet18')")

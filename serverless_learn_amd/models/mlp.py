@@ -29,7 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 # (the rules' semantics live there)
-from ..ops.optim import OptSpec, adamw_update, check_accum_steps, clip_grad_, lr_at, sgd_update  # noqa: F401
+from ..ops.optim import (OptSpec, adamw_update, check_accum_steps, clip_grad_, ema_update_, lr_at,  # noqa: F401
+                         sgd_update)
 from ..utils.graphs import GraphSlots
 
 D_IN = 784
@@ -160,7 +161,9 @@ def reference_grads_bf16(flat: torch.Tensor, x_u8: torch.Tensor, y: torch.Tensor
 class OptStateCPU:
     """Optimizer state of the CPU trainers beyond ``params`` / ``mom``: AdamW's second moment
     ``v`` and the optimizer step ``opt_step`` (a 1-element tensor, so a regroup broadcasts it
-    with the rest), both only where the rule needs them."""
+    with the rest), both only where the rule needs them; with ``ema_decay > 0`` the averaged
+    parameters ``ema``, their update count ``ema_step`` and the coefficient table ``ema_tab``
+    (ops/optim.py ema_table).  This class is the weight EMA's definition on the trainers."""
 
     def _init_opt(self, kw: dict) -> None:
         self.opt = opt = OptSpec(lr=self.lr, momentum=self.momentum, weight_decay=self.weight_decay, **kw)
@@ -168,6 +171,11 @@ class OptStateCPU:
         self.v = torch.zeros_like(self.params) if opt.adamw else None
         self.opt_step = None if opt.plain else torch.zeros(1, dtype=torch.int32)
         self._grad_norm = None
+        self.ema = self.ema_step = self.ema_tab = None
+        if opt.emas:  # starts at the initial parameters (flat= included)
+            self.ema = self.params.clone()
+            self.ema_step = torch.zeros(1, dtype=torch.int32)
+            self.ema_tab = torch.from_numpy(opt.ema_table())
 
     def grad_norm(self) -> float | None:
         """The gradient's global L2 norm at the last step, before clipping (None: clipping off)."""
@@ -178,15 +186,34 @@ class OptStateCPU:
             self._grad_norm = clip_grad_(g, self.opt.clip_grad_norm)
         if self.opt_step is None:
             sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
-            return
-        self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]))
-        self.opt_step += 1
+        else:
+            self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]))
+            self.opt_step += 1
+        if self.ema is not None:  # once per update, on the parameters just written
+            t = min(int(self.ema_step[0]), self.ema_tab.numel() - 1)
+            ema_update_(self.ema, self.params, self.ema_tab[t])
+            self.ema_step += 1
+
+    def ema_flat(self) -> torch.Tensor:
+        """A copy of the averaged parameters (``ema_decay > 0``)."""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight EMA (ema_decay=0)")
+        return self.ema[:self.n_params].clone()
+
+    def _eval_weights(self, ema: bool) -> torch.Tensor:
+        """What ``evaluate(ema=...)`` runs on: the parameters or their average (only read)."""
+        if ema and self.ema is None:
+            raise ValueError("evaluate(ema=True): this trainer keeps no weight EMA (ema_decay=0)")
+        return self.ema if ema else self.params
 
     def _opt_state_extra(self, d: dict) -> dict:
         if self.opt_step is not None:
             d["opt_step"] = self.opt_step.double().cpu().numpy()
         if self.v is not None:
             d["exp_avg_sq"] = self.v[:self.n_params].double().cpu().numpy()
+        if self.ema is not None:
+            d["ema"] = self.ema[:self.n_params].double().cpu().numpy()
+            d["ema_step"] = self.ema_step.double().cpu().numpy()
         return d
 
     def _opt_load_state_extra(self, d: dict) -> None:
@@ -194,9 +221,16 @@ class OptStateCPU:
             self.opt_step.fill_(int(d["opt_step"][0]))
         if self.v is not None and "exp_avg_sq" in d:
             self.v[:self.n_params].copy_(torch.as_tensor(np.asarray(d["exp_avg_sq"]), dtype=torch.float32))
+        if self.ema is not None:
+            if "ema" in d and "ema_step" in d:
+                self.ema[:self.n_params].copy_(torch.as_tensor(np.asarray(d["ema"]), dtype=torch.float32))
+                self.ema_step.fill_(int(d["ema_step"][0]))
+            else:  # a checkpoint without one: the average starts over from the weights just loaded
+                self.ema.copy_(self.params)
+                self.ema_step.zero_()
 
     def _opt_buffers(self) -> list:
-        return [t for t in (self.v, self.opt_step) if t is not None]
+        return [t for t in (self.v, self.opt_step, self.ema, self.ema_step) if t is not None]
 
     def reset_optimizer_state(self) -> None:
         for t in (self.mom, self.v, self.opt_step):
@@ -314,6 +348,15 @@ class CPUTrainer(OptStateCPU):
         n = self.samples_per_step
         return StepStats(loss / n, correct / n, n)
 
+    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
+        """Mean loss / accuracy of the parameters (``ema=True``: of their average) over (x, y)."""
+        with torch.no_grad():
+            logits = MLP(self._eval_weights(ema))(x_u8)
+            y = y_u8.reshape(-1).long()
+            loss = F.cross_entropy(logits, y, reduction="mean")
+            acc = (logits.argmax(1) == y).float().mean()
+        return StepStats(float(loss), float(acc), int(y.numel()))
+
     def get_flat(self) -> torch.Tensor:
         return self.params.clone()
 
@@ -408,6 +451,18 @@ class FusedMLPTrainer(GraphSlots):
             self._build_lr_table()
         self.clip_partials = self.clip_norm = None
         self._init_clip()
+        # the weight EMA (ema_decay > 0): the averaged parameters, the number of EMA updates applied,
+        # the ticket word of the launch that advances it and the coefficient table (ops/optim.py
+        # ema_table); its shadow set for evaluate(ema=True) is allocated on first use
+        self.ema = self.ema_step = self.ema_ticket = self.ema_tab = self._ema_eval = None
+        if self.opt.emas:
+            from ..ops.optim import EMA_KERNELS, require_kernels
+
+            require_kernels(self.opt, *EMA_KERNELS)
+            self.ema = self.params.clone()  # (after flat=)
+            self.ema_step = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.ema_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._build_ema_table()
         bf = torch.bfloat16
         # W1's shadow is fp16: layer 1 multiplies the exact pixels (fp16 1024 + u) and corrects the
         # offset with the W1 row sums, kept as 64-bit fixed-point partials (mlp_fused.hip, R1_BLK)
@@ -531,6 +586,9 @@ class FusedMLPTrainer(GraphSlots):
         tab = self.opt.lr_table()
         self.lr_tab = torch.from_numpy(tab).to(self.device) if tab is not None else None
 
+    def _build_ema_table(self) -> None:
+        self.ema_tab = torch.from_numpy(self.opt.ema_table()).to(self.device)
+
     def _init_clip(self) -> None:
         """Gradient clipping's scratch (the workgroups' fp64 partial sums) and the norm it reports."""
         if self.opt.clips and self.clip_norm is None:
@@ -551,12 +609,16 @@ class FusedMLPTrainer(GraphSlots):
         new = dataclasses.replace(self.opt, **kw)
         if (new.adamw, new.plain) != (self.opt.adamw, self.opt.plain):
             raise ValueError("the optimizer rule is fixed at construction (build a new trainer)")
+        if new.emas != self.opt.emas:
+            raise ValueError("the weight EMA is switched on or off at construction (build a new trainer)")
         if new.clips and self.xgmi is not None:
             raise ValueError("gradient clipping is not available with the xGMI exchange")
         self.opt = new
         self.lr, self.momentum, self.weight_decay = new.lr, new.momentum, new.weight_decay
         if not new.plain:
             self._build_lr_table()
+        if new.emas:
+            self._build_ema_table()
         self._init_clip()
         self.graph = None
         self._lkey = None
@@ -570,7 +632,8 @@ class FusedMLPTrainer(GraphSlots):
                self.n_batches, self.grad_scale, self.lr,
                self.momentum, self.weight_decay, id(self.xgmi), bool(self.xgmi and self.xgmi.two_shot),
                self.xgmi.inline_sync if self.xgmi is not None else None, None if self.opt.plain else self.opt,
-               self.opt.clip_grad_norm, self.accum_steps)
+               self.opt.clip_grad_norm, self.accum_steps,
+               (self.opt.ema_decay, self.opt.ema_warmup) if self.opt.emas else None)
         if getattr(self, "_lkey", None) == key:
             return self._lc
         n, p = self._n, self._n.ptr
@@ -618,6 +681,9 @@ class FusedMLPTrainer(GraphSlots):
                 lc[name] = [n.Launch("sl_accum_flat", p(a), p(t), cnt, add) for a, t, cnt in pairs]
             lc["acc_fold"] = [n.Launch("sl_accum_flat", p(t), p(a), cnt, 1) for a, t, cnt in pairs]
             lc["bump"] = n.Launch("sl_cursor_bump", p(self.cursor))
+        if self.opt.emas:  # after the update launch of every step path; advances ema_step itself
+            lc["ema"] = n.Launch("sl_ema_flat", p(self.ema), p(self.params), N_PARAMS, p(self.ema_step),
+                                 p(self.ema_ticket), p(self.ema_tab), self.ema_tab.numel())
         if self.xgmi is not None:
             xg = self.xgmi
             # inline synchronisation: the reduce publishes the step, the update waits per workgroup
@@ -753,6 +819,8 @@ class FusedMLPTrainer(GraphSlots):
             if self.opt.clips:  # the whole norm before any weight moves: the fused slab update cannot clip
                 self._launches()["clip"]()
             self._sgd(2, from_grad=True, grad_out=False)
+        if self.ema is not None:  # local, so also behind the xGMI update
+            self._launches()["ema"]()
         ph.mark("update")
 
     def _step_accum(self) -> None:
@@ -774,6 +842,8 @@ class FusedMLPTrainer(GraphSlots):
         if self.opt.clips:
             lc["clip"]()
         lc["update"]()
+        if self.ema is not None:
+            lc["ema"]()
         ph.mark("update")
 
     def grad_norm(self) -> float | None:
@@ -839,32 +909,60 @@ class FusedMLPTrainer(GraphSlots):
         n = self.samples_per_step  # (an accumulated step leaves the sums over its micro-batches in loss / correct)
         return StepStats(loss / n, acc / n, n)
 
-    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> StepStats:
+    def ema_flat(self) -> torch.Tensor:
+        """A copy of the averaged parameters (``ema_decay > 0``)."""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight EMA (ema_decay=0)")
+        return self.ema[:N_PARAMS].clone()
+
+    def _eval_set(self, ema: bool) -> dict:
+        """The weights an evaluation launch reads: the training set, or with ``ema`` a second set
+        of shadows (allocated on first use) rebuilt from the averaged parameters by the launch that
+        ``refresh_shadows`` uses -- what a second trainer holds after ``set_flat(ema_flat())``.  No
+        training tensor is written or moved, so a captured graph stays valid."""
+        names = ("w1h", "w2h", "w2th", "w3h", "w3th", "r1p")
+        if not ema:
+            return dict({k: getattr(self, k) for k in names}, params=self.params)
+        if self.ema is None:
+            raise ValueError("ema=True: this trainer keeps no weight EMA (ema_decay=0)")
+        if self._ema_eval is None:
+            self._ema_eval = {k: torch.zeros_like(getattr(self, k)) for k in names}
+        s, n = self._ema_eval, self._n
+        n.call("sl_mlp_sgd", n.ptr(self.ema), None, None, 0, 0, None, None, 0.0, 0.0, 0.0, self.xa, self.xb, 0,
+               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w2th"]), n.ptr(s["w3h"]), n.ptr(s["w3th"]),
+               None, n.ptr(s["r1p"]), n.stream_ptr())
+        return dict(s, params=self.ema)
+
+    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
+        """Mean loss / accuracy over the whole 64-row blocks of (x, y); ``ema=True``: of the
+        averaged parameters, the training state untouched (between steps)."""
         n = self._n
+        s = self._eval_set(ema)
         x = x_u8.reshape(-1, D_IN).to(self.device).contiguous()
         y = y_u8.reshape(-1).to(self.device).to(torch.uint8).contiguous()
         rows = x.shape[0] // BLOCK_ROWS * BLOCK_ROWS
         loss = torch.zeros(rows, device=self.device)
         corr = torch.zeros(rows, device=self.device)
         n.call("sl_mlp_rows", n.ptr(x), n.ptr(y), None, 1, rows,
-               n.ptr(self.w1h), n.ptr(self.w2h), n.ptr(self.w3h), n.ptr(self.w2th), n.ptr(self.w3th),
-               n.ptr(self.params), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
-               n.ptr(loss), n.ptr(corr), None, 0, n.ptr(self.r1p), None, n.stream_ptr())
-        lv = float("nan") if self.w1_out_of_range() else float(loss.mean())
+               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w3h"]), n.ptr(s["w2th"]), n.ptr(s["w3th"]),
+               n.ptr(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
+               n.ptr(loss), n.ptr(corr), None, 0, n.ptr(s["r1p"]), None, n.stream_ptr())
+        lv = float("nan") if int(s["r1p"].max()) >= R1_OVF_MIN else float(loss.mean())
         return StepStats(lv, float(corr.mean()), rows)
 
-    def logits(self, x_u8: torch.Tensor) -> torch.Tensor:
+    def logits(self, x_u8: torch.Tensor, ema: bool = False) -> torch.Tensor:
         n = self._n
+        s = self._eval_set(ema)
         x = x_u8.reshape(-1, D_IN).to(self.device).contiguous()
         rows = x.shape[0]
         if rows % BLOCK_ROWS:
             raise ValueError(f"rows must be a multiple of {BLOCK_ROWS}")
         out = torch.empty(rows, CLASSES, device=self.device)
         n.call("sl_mlp_rows", n.ptr(x), None, None, 1, rows,
-               n.ptr(self.w1h), n.ptr(self.w2h), n.ptr(self.w3h), n.ptr(self.w2th), n.ptr(self.w3th),
-               n.ptr(self.params), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
-               None, None, n.ptr(out), 0, n.ptr(self.r1p), None, n.stream_ptr())
-        if self.w1_out_of_range():
+               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w3h"]), n.ptr(s["w2th"]), n.ptr(s["w3th"]),
+               n.ptr(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
+               None, None, n.ptr(out), 0, n.ptr(s["r1p"]), None, n.stream_ptr())
+        if int(s["r1p"].max()) >= R1_OVF_MIN:
             out.fill_(float("nan"))
         return out
 
@@ -884,6 +982,9 @@ class FusedMLPTrainer(GraphSlots):
             d["opt_step"] = self.opt_step.double().cpu().numpy()  # travels as the momentum section)
         if self.v is not None:
             d["exp_avg_sq"] = self.v[:N_PARAMS].double().cpu().numpy()
+        if self.ema is not None:  # the averaged parameters and the number of EMA updates behind them
+            d["ema"] = self.ema[:N_PARAMS].double().cpu().numpy()
+            d["ema_step"] = self.ema_step.double().cpu().numpy()
         return d
 
     def load_state_extra(self, d: dict) -> None:
@@ -895,10 +996,19 @@ class FusedMLPTrainer(GraphSlots):
             self.opt_ticket.zero_()
         if self.v is not None and "exp_avg_sq" in d:
             self.v[:N_PARAMS].copy_(torch.as_tensor(np.asarray(d["exp_avg_sq"]), dtype=torch.float32))
+        if self.ema is not None:
+            if "ema" in d and "ema_step" in d:
+                self.ema[:N_PARAMS].copy_(torch.as_tensor(np.asarray(d["ema"]), dtype=torch.float32))
+                self.ema_step.fill_(int(d["ema_step"][0]))
+            else:  # a checkpoint without one: the average starts over from the weights just loaded
+                self.ema.copy_(self.params)
+                self.ema_step.zero_()
+            self.ema_ticket.zero_()
 
     def buffers(self) -> list:
-        """Optimizer state beyond params / mom, broadcast with them after a regroup."""
-        return [t for t in (self.v, self.opt_step) if t is not None]
+        """Optimizer state beyond params / mom (and the weight EMA), broadcast with them after a
+        regroup."""
+        return [t for t in (self.v, self.opt_step, self.ema, self.ema_step) if t is not None]
 
     def reset_optimizer_state(self) -> None:
         for t in (self.mom, self.v, self.opt_step, self.opt_ticket):

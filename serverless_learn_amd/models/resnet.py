@@ -389,12 +389,13 @@ class CPUResNetTrainer(OptStateCPU):
         """Non-parameter state every replica must agree on (broadcast after a regroup)."""
         return [t for pair in self.running.values() for t in pair] + self._opt_buffers()
 
-    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor):
-        """Inference with the BatchNorm running statistics (eval mode)."""
+    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False):
+        """Inference with the BatchNorm running statistics (eval mode); ``ema=True``: of the averaged
+        parameters, with the same running statistics (those are not averaged)."""
         from .mlp import StepStats
 
         with torch.no_grad():
-            logits = ref_forward(self.spec, self.params, x_u8.reshape(-1, self.spec.in_hw, self.spec.in_hw, 3),
+            logits = ref_forward(self.spec, self._eval_weights(ema), x_u8.reshape(-1, self.spec.in_hw, self.spec.in_hw, 3),
                                  False, self.running)
             y = y_u8.reshape(-1).long()
             loss = F.cross_entropy(logits, y, reduction="mean")

@@ -30,7 +30,8 @@ Per step:
             backward continues
   update    one multi-tensor SGD launch over the flat vector (fp32 master,
             momentum, weight decay, bf16 shadow) + one launch that re-lays the
-            bf16 conv weights out for dgrad.
+            bf16 conv weights out for dgrad; with ema_decay= on, one launch
+            between them that moves the weight EMA towards the new parameters.
 """
 from __future__ import annotations
 
@@ -135,6 +136,16 @@ class FusedResNetTrainer(GraphSlots):
             O.require_kernels(self.opt, *O.CLIP_KERNELS)
             self.clip_partials, self.clip_norm = O.clip_buffers(n, dev)
         self.shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
+        # the weight EMA (ema_decay > 0): the averaged parameters, the number of EMA updates applied,
+        # the ticket word of the launch that advances it and the coefficient table (ops/optim.py
+        # ema_table).  BatchNorm running statistics are not averaged: they already are a moving average
+        self.ema = self.ema_step = self.ema_ticket = self.ema_tab = None
+        if self.opt.emas:
+            O.require_kernels(self.opt, *O.EMA_KERNELS)
+            self.ema = self.params.clone()  # (after flat=)
+            self.ema_step = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.ema_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.ema_tab = torch.from_numpy(self.opt.ema_table()).to(dev)
         bns = list(spec.bns())
         rsz = {b.name: (K.rsum_floats(2 * b.c) + 3) // 4 * 4 for b in bns}  # 16-B aligned regions
         self.arena = torch.zeros(sum(2 * rsz[b.name] for b in bns), device=dev)
@@ -529,6 +540,8 @@ class FusedResNetTrainer(GraphSlots):
         if self.opt.clips:  # on the aggregated gradient, before the unchanged update rule
             self.O.clip_grad_norm_flat(self.grad, self.opt.clip_grad_norm, self.clip_partials, self.clip_norm)
         self._update()
+        if self.ema is not None:  # on the parameters just written; the launch advances ema_step itself
+            self.O.ema_flat(self.ema, self.params, self.ema_step, self.ema_ticket, self.ema_tab)
         self.wt()
         self.K.cursor_bump(self.cursor)
         self.phases.mark("update")
@@ -609,6 +622,12 @@ class FusedResNetTrainer(GraphSlots):
         self.params.copy_(flat.to(self.params))
         self.refresh_shadows()
 
+    def ema_flat(self) -> torch.Tensor:
+        """A copy of the averaged parameters (``ema_decay > 0``)."""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight EMA (ema_decay=0)")
+        return self.ema.clone()
+
     def running_stats(self) -> dict:
         return {name: (b.run_mean, b.run_var) for name, b in self.bn.items()}
 
@@ -622,6 +641,9 @@ class FusedResNetTrainer(GraphSlots):
             d["opt_step"] = self.opt_step.double().cpu().numpy()  # travels as the momentum section)
         if self.v is not None:
             d["exp_avg_sq"] = self.v.double().cpu().numpy()
+        if self.ema is not None:  # the averaged parameters and the number of EMA updates behind them
+            d["ema"] = self.ema.double().cpu().numpy()
+            d["ema_step"] = self.ema_step.double().cpu().numpy()
         return d
 
     def load_state_extra(self, d: dict) -> None:
@@ -635,12 +657,21 @@ class FusedResNetTrainer(GraphSlots):
             self.opt_step.fill_(int(d["opt_step"][0]))
         if self.v is not None and "exp_avg_sq" in d:
             self.v.copy_(torch.as_tensor(d["exp_avg_sq"], dtype=torch.float32))
+        if self.ema is not None:
+            if "ema" in d and "ema_step" in d:
+                self.ema.copy_(torch.as_tensor(d["ema"], dtype=torch.float32))
+                self.ema_step.fill_(int(d["ema_step"][0]))
+            else:  # a checkpoint without one: the average starts over from the weights just loaded
+                self.ema.copy_(self.params)
+                self.ema_step.zero_()
+            self.ema_ticket.zero_()
 
     def buffers(self) -> list:
         """BN running statistics: broadcast with the parameters after a regroup, so every
-        replica evaluates identically (each rank's statistics come from its own batches)."""
+        replica evaluates identically (each rank's statistics come from its own batches); the
+        optimizer state beyond params / mom and the weight EMA likewise."""
         bufs = [t for b in self.bn.values() for t in (b.run_mean, b.run_var)]
-        return bufs + [t for t in (self.v, self.opt_step) if t is not None]
+        return bufs + [t for t in (self.v, self.opt_step, self.ema, self.ema_step) if t is not None]
 
     def reset_optimizer_state(self) -> None:
         for t in (self.mom, self.v, self.opt_step):
@@ -682,9 +713,25 @@ class FusedResNetTrainer(GraphSlots):
         K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
                      None, self.grad_scale)
 
-    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> StepStats:
+    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
         """Eval-mode loss / accuracy over every whole batch of (x, y) with the running
-        statistics; the training shard, cursor and statistics are left untouched."""
+        statistics; the training shard, cursor and statistics are left untouched.  ``ema=True``:
+        of the averaged parameters, with the same running statistics -- what a second trainer
+        returns after ``set_flat(ema_flat())``.  The parameters' contents are swapped for the
+        average's and put back (with the bf16 shadow; the transposed weights are rebuilt from it), so
+        no tensor moves and a captured graph stays valid.  Between steps only."""
+        if ema:
+            if self.ema is None:
+                raise ValueError("evaluate(ema=True): this trainer keeps no weight EMA (ema_decay=0)")
+            keep = (self.params.clone(), self.shadow.clone())
+            self.params.copy_(self.ema)
+            self.refresh_shadows()
+            try:
+                return self.evaluate(x_u8, y_u8)
+            finally:
+                self.params.copy_(keep[0])
+                self.shadow.copy_(keep[1])
+                self.wt()
         hw = self.spec.in_hw
         x = x_u8.reshape(-1, hw, hw, 3).to(self.device).contiguous()
         y = y_u8.reshape(-1).to(self.device).to(torch.uint8).contiguous()

@@ -14,6 +14,10 @@ Either rule may be preceded by global-norm gradient clipping (``clip_grad_norm``
 
 Gradient accumulation (``accum_steps`` micro-batches per update) sums the micro-gradients ahead of
 all that with :func:`accum_flat`, one fp32 add per element in a fixed order.
+
+A weight EMA (``ema_decay``) follows every update: :func:`ema_update_` is its reference,
+:func:`ema_table` the per-step coefficients and :func:`ema_flat` the one launch that applies them and
+advances its own device-resident counter.
 """
 from __future__ import annotations
 
@@ -40,6 +44,7 @@ _STEP = [N.P, N.P, N.P, N.I]  # step, ticket, lr table, its length
 N.register("sl_clip_grad_partials", [N.L])
 N.register("sl_clip_grad_norm", [N.P, N.L, N.F, N.P, N.I, N.P, N.P])
 N.register("sl_accum_flat", [N.P, N.P, N.L, N.I, N.P])
+N.register("sl_ema_flat", [N.P, N.P, N.L, N.P, N.P, N.P, N.I, N.P])
 N.register("sl_cursor_bump", [N.P, N.P])  # (ops/cnn.py's launcher: the MLP's accumulated step bumps its cursor with it)
 N.register("sl_mlp_opt", [N.I, N.P, N.P, N.P, N.P, N.I, N.L, N.P, N.F, N.F, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P,
                           N.P, N.P, *_STEP, *_ADAM, N.P])
@@ -102,6 +107,64 @@ def clip_grad_(g: torch.Tensor, max_norm: float) -> float:
     return total
 
 
+EMA_WARMUP_OFFSET = 10   # warm-up: decay_t = min(decay, (1 + t) / (10 + t))
+EMA_TABLE_MAX = 1 << 20  # entries of the warm-up table
+
+
+def _ema_last(decay: float, warmup: bool) -> int:
+    """T: the first update ``t`` at which the warm-up ``(1 + t) / (10 + t)`` has reached ``decay``
+    (0 with warm-up off), ``max(0, ceil((10 D - 1) / (1 - D)))``; refuses a bad decay and a table
+    past :data:`EMA_TABLE_MAX`."""
+    d = float(decay)
+    if not 0.0 <= d < 1.0:  # negative, NaN, or no averaging at all
+        raise ValueError(f"ema_decay must be in [0, 1) (0: off), got {decay!r}")
+    if not warmup or d == 0.0:
+        return 0
+    if (EMA_WARMUP_OFFSET * d - 1.0) / (1.0 - d) > EMA_TABLE_MAX:
+        raise ValueError(f"ema_decay {decay!r}: its warm-up table would be longer than {EMA_TABLE_MAX} entries "
+                         "(turn ema_warmup off)")
+    reached = lambda t: (1 + t) / (EMA_WARMUP_OFFSET + t) >= d  # noqa: E731
+    last = max(0, math.ceil((EMA_WARMUP_OFFSET * d - 1.0) / (1.0 - d)))
+    while last > 0 and reached(last - 1):  # (the closed form, in floating point, may be one off)
+        last -= 1
+    while not reached(last):
+        last += 1
+    if last + 1 > EMA_TABLE_MAX:
+        raise ValueError(f"ema_decay {decay!r}: its warm-up table would be longer than {EMA_TABLE_MAX} entries "
+                         "(turn ema_warmup off)")
+    return last
+
+
+def ema_table_len(decay: float, warmup: bool = True) -> int:
+    """Entries of :func:`ema_table` (0 with the EMA off); refuses what it refuses."""
+    last = _ema_last(decay, warmup)
+    return 0 if float(decay) == 0.0 else last + 1
+
+
+def ema_table(decay: float, warmup: bool = True) -> np.ndarray:
+    """``float32(1 - d_t)`` for EMA updates ``t = 0 .. T`` (each computed in float64 and rounded
+    once), where ``d_t = min(decay, (1 + t) / (10 + t))`` with warm-up and ``decay`` without, and
+    ``T`` is the first ``t`` at which the warm-up has reached ``decay``: every later update has the
+    last entry's value, so the table is indexed with ``min(t, T)`` as ``lr_tab`` is.  Without
+    warm-up it has one entry."""
+    last = _ema_last(decay, warmup)
+    if float(decay) == 0.0:
+        raise ValueError("ema_decay 0 is off: there is no table")
+    t = np.arange(last + 1, dtype=np.float64)
+    d_t = np.minimum(float(decay), (1.0 + t) / (EMA_WARMUP_OFFSET + t)) if warmup else np.full(1, float(decay))
+    return (1.0 - d_t).astype(np.float32)
+
+
+def ema_update_(ema: torch.Tensor, w: torch.Tensor, omd) -> None:
+    """The weight EMA's reference, in place: ``e <- e + omd * (w - e)`` as three fp32 operations,
+    each rounded once (subtract, multiply, add; no fma), with ``omd = float32(1 - decay_t)``.
+    ``w == e`` leaves ``e`` unchanged."""
+    assert ema.dtype == torch.float32 and w.dtype == torch.float32 and ema.shape == w.shape
+    d = torch.sub(w, ema)
+    d.mul_(torch.as_tensor(omd, dtype=torch.float32, device=d.device))
+    ema.add_(d)
+
+
 @dataclass(frozen=True)
 class OptSpec:
     """The optimizer hyper-parameters a trainer is built with (its keyword arguments)."""
@@ -117,6 +180,8 @@ class OptSpec:
     lr_decay_steps: int = 0
     lr_min_ratio: float = 0.0
     clip_grad_norm: float = 0.0  # max global L2 norm of the gradient (0: off; inf: measure only)
+    ema_decay: float = 0.0       # weight EMA after every update (0: off); no rule or kernel choice depends on it
+    ema_warmup: bool = True      # decay_t = min(ema_decay, (1 + t) / (10 + t))
 
     def __post_init__(self):
         if self.optimizer not in OPTIMIZERS:
@@ -132,10 +197,19 @@ class OptSpec:
             raise ValueError("adamw needs 0 < beta1, beta2 < 1 and adam_eps > 0")
         if not self.clip_grad_norm >= 0.0:  # negative or NaN
             raise ValueError("clip_grad_norm must be >= 0 (0: off, inf: measure the norm only)")
+        _ema_last(self.ema_decay, self.ema_warmup)  # a bad decay, a warm-up table that is too long
 
     @property
     def clips(self) -> bool:
         return self.clip_grad_norm > 0.0
+
+    @property
+    def emas(self) -> bool:
+        return self.ema_decay > 0.0
+
+    def ema_table(self) -> np.ndarray | None:
+        """:func:`ema_table` of this spec; None with the EMA off."""
+        return ema_table(self.ema_decay, self.ema_warmup) if self.emas else None
 
     @property
     def adamw(self) -> bool:
@@ -192,19 +266,21 @@ class OptSpec:
                      decay_steps=self.lr_decay_steps, min_ratio=self.lr_min_ratio)
         if self.clips:
             d["clip_grad_norm"] = self.clip_grad_norm
+        if self.emas:
+            d.update(ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup))
         return d
 
 
 def require_kernels(spec: OptSpec, *names: str) -> None:
-    """The step-counter rules, gradient clipping and gradient accumulation need their entry
-    points: an older kernel build (kept for A/B runs of the SGD path) does not have them, and
+    """The step-counter rules, gradient clipping, gradient accumulation and the weight EMA need
+    their entry points: an older kernel build (kept for A/B runs of the SGD path) does not have them, and
     there is no fallback."""
     lib = N.lib()
     missing = [n for n in names if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"optimizer {spec.optimizer!r} / lr_schedule {spec.lr_schedule!r} / clip_grad_norm "
-                           f"{spec.clip_grad_norm!r} / accum_steps > 1 need {', '.join(missing)}: not in this "
-                           "kernel library")
+                           f"{spec.clip_grad_norm!r} / accum_steps > 1 / ema_decay {spec.ema_decay!r} need "
+                           f"{', '.join(missing)}: not in this kernel library")
 
 
 # ---- flat kernels ----
@@ -293,3 +369,22 @@ def accum_flat(dst: torch.Tensor, src: torch.Tensor, add) -> None:
     nbytes, a, b = 4 * dst.numel(), dst.data_ptr(), src.data_ptr()
     assert a + nbytes <= b or b + nbytes <= a, "accum_flat: dst and src overlap"
     N.call("sl_accum_flat", a, b, dst.numel(), int(bool(add)), N.stream_ptr())
+
+
+EMA_KERNELS = ("sl_ema_flat",)
+
+
+def ema_flat(ema: torch.Tensor, w: torch.Tensor, step: torch.Tensor, ticket: torch.Tensor, tab: torch.Tensor) -> None:
+    """:func:`ema_update_` on the device in one launch (csrc/kernels/elementwise.hip): ``ema +=
+    tab[min(step, len - 1)] * (w - ema)`` in three fp32 roundings, then ``step += 1`` (``step``:
+    int32 on the device; ``ticket``: a zeroed int32 word the launch uses to find its last workgroup
+    and leaves at zero).  No host synchronisation, so a captured graph replays it with a moving
+    coefficient; the same bits from call to call and in both kernel builds.  ``ema`` and ``w`` are
+    whole 16-byte-aligned fp32 vectors of one length that do not overlap."""
+    assert ema.is_cuda and w.is_cuda and ema.dtype == torch.float32 and w.dtype == torch.float32
+    assert ema.is_contiguous() and w.is_contiguous() and ema.numel() == w.numel()
+    assert step.dtype == torch.int32 and ticket.dtype == torch.int32 and step.numel() == 1 and ticket.numel() == 1
+    assert tab.dtype == torch.float32 and tab.is_contiguous() and tab.numel() >= 1
+    nbytes, a, b = 4 * ema.numel(), ema.data_ptr(), w.data_ptr()
+    assert a + nbytes <= b or b + nbytes <= a, "ema_flat: ema and w overlap"
+    N.call("sl_ema_flat", a, b, ema.numel(), N.ptr(step), N.ptr(ticket), N.ptr(tab), tab.numel(), N.stream_ptr())

@@ -161,7 +161,11 @@ class Worker:
             kw.update(label_smoothing=c.label_smoothing, mixup_alpha=c.mixup_alpha, cutmix_alpha=c.cutmix_alpha)
         if c.accum_for(world) != 1:  # accum_steps, or the K nearest to global_batch at this world
             kw.update(accum_steps=c.accum_for(world))
+        if c.ema_decay != 0:  # (a bad decay is refused by Config and by OptSpec)
+            kw.update(ema_decay=c.ema_decay, ema_warmup=c.ema_warmup)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
+        if c.ema_decay != 0:
+            self.log.info("ema", decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
 
@@ -330,8 +334,13 @@ class Worker:
                 self.trainer.reset_optimizer_state()
             if mom is not None and self.trainer.mom is not None:
                 self.trainer.mom[:self.trainer.n_params].copy_(torch.from_numpy(mom))
-            if extra and hasattr(self.trainer, "load_state_extra"):
-                self.trainer.load_state_extra(extra)  # batch cursor, BN running statistics, optimizer step, v
+            ema_missing = getattr(self.trainer, "ema", None) is not None and not {"ema", "ema_step"} <= set(extra)
+            if (extra or ema_missing) and hasattr(self.trainer, "load_state_extra"):
+                # batch cursor, BN running statistics, optimizer step, v, the weight EMA (absent from
+                # the file: it starts over from the weights just loaded)
+                self.trainer.load_state_extra(extra)
+            if ema_missing:
+                self.log.warn("checkpoint_ema_missing", ckpt_step=meta.get("step"))
             self.trainer.graph = None  # a captured graph holds the old state's launches
             self.step = int(meta.get("step", 0))
             self.resumed_step = self.step
