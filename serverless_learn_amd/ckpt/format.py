@@ -33,6 +33,7 @@ from ..wire.codec import decode_update, encode_update
 
 MAGIC = b"SLCKPT01"
 CKPT_BASE = 1 << 31
+EVAL_BASE = 1 << 30  # file numbers in [EVAL_BASE, CKPT_BASE) are held-out shards; EVAL_BASE is the validation shard
 _HDR = struct.Struct("<8sII")
 _LEN = struct.Struct("<Q")
 

@@ -81,6 +81,11 @@ class Config:
     mixup_alpha: float = 0.0           # resnet18: mixup with lambda ~ Beta(alpha, alpha) per batch (0 = off)
     cutmix_alpha: float = 0.0          # resnet18: CutMix likewise; with both on, one of the two per batch
     seed: int = 0
+    eval_every: int = 0                # > 0: every this many steps, evaluate on the held-out shard (file EVAL_BASE,
+                                       # pushed once per worker); 0 = off
+    eval_records: int = 10_000         # records of the held-out shard (1..2^22)
+    eval_topk: int = 5                 # the k of the reported top-k accuracy (1..10)
+    eval_seed: int = -1                # seed of the held-out records; -1 = seed + 1 (never equal to seed)
     checkpoint_every: int = 0          # steps between checkpoints (rank 0); 0 = off
     max_steps: int = 0                 # 0 = run until stopped
     log_every: int = 50
@@ -109,7 +114,9 @@ class Config:
 
     def validate(self) -> None:
         """Refuse combinations no component implements (gradient accumulation's, the weight EMA's,
-        the input pipeline's, the soft-target loss's and the top-k sparse gossip's)."""
+        the input pipeline's, the soft-target loss's, held-out evaluation's and the top-k sparse
+        gossip's)."""
+        self._validate_eval()
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
         if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:
@@ -148,6 +155,29 @@ class Config:
             raise ValueError("gossip_topk: the simulate model is growable and is never sparse")
         if self.gossip_compat:
             raise ValueError("gossip_topk: gossip_compat reproduces the reference's dense exchange byte for byte")
+
+    def _validate_eval(self) -> None:
+        def integer(name, lo, hi=None):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or v < lo or (hi is not None and v > hi):
+                rng = f"in {lo}..{hi}" if hi is not None else f">= {lo}"
+                raise ValueError(f"{name} must be an integer {rng}, got {v!r}")
+
+        integer("eval_every", 0)
+        integer("eval_records", 1, 1 << 22)  # (the int64 loss sum of ops/evalmetrics.py holds that many)
+        integer("eval_topk", 1, 10)
+        if self.held_out_seed == self.seed:
+            raise ValueError(f"eval_seed {self.eval_seed} equals seed: the held-out records would be training records")
+        if self.eval_every > 0 and self.model == "simulate":
+            raise ValueError("eval_every: the simulate model has nothing to evaluate")
+        if self.eval_every > 0 and self.dataset == "reference-dummy":
+            raise ValueError("eval_every: the reference-dummy dataset has no held-out set")
+
+    @property
+    def held_out_seed(self) -> int:
+        """The seed of the held-out shard's records: ``eval_seed``, by default ``seed + 1`` (the field
+        stays -1, so a later change of ``seed`` moves it along)."""
+        return self.seed + 1 if self.eval_seed == -1 else self.eval_seed
 
     def accum_for(self, world: int) -> int:
         """Micro-batches per step in a lock-step group of ``world`` workers: ``accum_steps``, or with

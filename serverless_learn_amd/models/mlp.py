@@ -357,6 +357,21 @@ class CPUTrainer(OptStateCPU):
             acc = (logits.argmax(1) == y).float().mean()
         return StepStats(float(loss), float(acc), int(y.numel()))
 
+    def evaluate_full(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False, topk: int = 5):
+        """The held-out report (ops/evalmetrics.py EvalReport) of the parameters (``ema=True``: of
+        their average) over every record of (x, y): the logits of :meth:`evaluate`, the fp32 per-row
+        cross-entropy, and the definition itself."""
+        from ..ops.evalmetrics import check_records, check_topk, eval_reference
+
+        topk = check_topk(topk, CLASSES)
+        w = self._eval_weights(ema)
+        y = y_u8.reshape(-1).long()
+        check_records(int(y.numel()))
+        with torch.no_grad():
+            logits = MLP(w)(x_u8)
+            rows = F.cross_entropy(logits, torch.where(y < CLASSES, y, 0), reduction="none").float()
+        return eval_reference(logits, y, rows, CLASSES, topk)
+
     def get_flat(self) -> torch.Tensor:
         return self.params.clone()
 
@@ -965,6 +980,37 @@ class FusedMLPTrainer(GraphSlots):
         if int(s["r1p"].max()) >= R1_OVF_MIN:
             out.fill_(float("nan"))
         return out
+
+    def evaluate_full(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False, topk: int = 5):
+        """The held-out report (ops/evalmetrics.py EvalReport) over every record of (x, y), padded
+        with zero rows to whole 64-row blocks: one evaluation-form rows launch writes the per-row loss
+        and the logits, one ``sl_eval_accum`` launch over all rows with ``n_valid = N`` counts them on
+        the device, and the 264-word block is read once.  ``ema=True``: of the averaged parameters;
+        the training state is untouched (between steps).  A W1 weight beyond fp16 (``stats``' rule)
+        makes every row bad and the loss NaN."""
+        from ..ops import evalmetrics as E
+
+        n = self._n
+        topk = E.check_topk(topk, CLASSES)
+        y = y_u8.reshape(-1)
+        N = E.check_records(int(y.numel()))
+        x = x_u8.reshape(N, D_IN)
+        s = self._eval_set(ema)
+        rows = (N + BLOCK_ROWS - 1) // BLOCK_ROWS * BLOCK_ROWS
+        xp = torch.zeros(rows, D_IN, dtype=torch.uint8, device=self.device)
+        yp = torch.zeros(rows, dtype=torch.uint8, device=self.device)
+        xp[:N].copy_(x)
+        yp[:N].copy_(y)
+        loss = torch.empty(rows, device=self.device)
+        out = torch.empty(rows, CLASSES, device=self.device)
+        acc = E.new_acc(self.device)
+        n.call("sl_mlp_rows", n.ptr(xp), n.ptr(yp), None, 1, rows,
+               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w3h"]), n.ptr(s["w2th"]), n.ptr(s["w3th"]),
+               n.ptr(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
+               n.ptr(loss), None, n.ptr(out), 0, n.ptr(s["r1p"]), None, n.stream_ptr())
+        E.eval_accum(out, yp, loss, N, CLASSES, topk, acc)
+        rep = E.report_from_acc(acc, CLASSES, topk)
+        return rep.all_bad() if int(s["r1p"].max()) >= R1_OVF_MIN else rep
 
     def get_flat(self) -> torch.Tensor:
         return self.params[:N_PARAMS].clone()

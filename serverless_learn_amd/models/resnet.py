@@ -402,6 +402,27 @@ class CPUResNetTrainer(OptStateCPU):
             acc = (logits.argmax(1) == y).float().mean()
         return StepStats(float(loss), float(acc), int(y.numel()))
 
+    def evaluate_full(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False, topk: int = 5):
+        """The held-out report (ops/evalmetrics.py EvalReport) over every record of (x, y): the
+        logits of :meth:`evaluate`, the fp32 per-row cross-entropy, and the definition itself."""
+        from ..ops.evalmetrics import check_records, check_topk, eval_reference
+
+        ncls = self.spec.classes
+        topk = check_topk(topk, ncls)
+        w = self._eval_weights(ema)
+        y = y_u8.reshape(-1).long()
+        n = check_records(int(y.numel()))
+        x = x_u8.reshape(-1, self.spec.in_hw, self.spec.in_hw, 3)
+        rep = None
+        with torch.no_grad():
+            for s in range(0, n, 1024):  # (running statistics: the rows are independent, and reports add)
+                ys = y[s:s + 1024]
+                logits = ref_forward(self.spec, w, x[s:s + 1024], False, self.running)
+                rows = F.cross_entropy(logits, torch.where(ys < ncls, ys, 0), reduction="none").float()
+                part = eval_reference(logits, ys, rows, ncls, topk)
+                rep = part if rep is None else rep + part
+        return rep
+
 
 def block_backward_errors(tr, g: torch.Tensor) -> list:
     """Per residual block of a FusedResNetTrainer that just ran ``compute_grads`` (returned

@@ -35,6 +35,7 @@ Per step:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import torch
 
@@ -88,13 +89,15 @@ class FusedResNetTrainer(GraphSlots):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
+        from ..ops import evalmetrics as E
         from ..ops import optim as O
 
         self.spec = spec = resnet18_spec(stem, classes, in_hw)
         A.check(augment, augment_pad, spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         _native.lib()
-        self.K, self.O = K, O
+        self.K, self.O, self.E = K, O, E
+        self._eval_cache = None  # evaluate_full's padded device copy of the last set passed
         # the training input pipeline (data/augment.py): a pure function of (seed, cursor, sample),
         # so the cursor that is checkpointed and broadcast already is all the state it has
         self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
@@ -751,3 +754,66 @@ class FusedResNetTrainer(GraphSlots):
             self.x, self.y, self.cursor = saved
         n = nb * self.batch
         return StepStats(loss / n, corr / n, n)
+
+    # ---- the held-out evaluation pass (ops/evalmetrics.py) ----
+    @contextlib.contextmanager
+    def _ema_weights(self):
+        """:meth:`evaluate`'s ``ema=True`` swap: the parameters' contents become the average's and are
+        put back (with the bf16 shadow; the transposed weights are rebuilt from it).  No tensor moves."""
+        if self.ema is None:
+            raise ValueError("evaluate(ema=True): this trainer keeps no weight EMA (ema_decay=0)")
+        keep = (self.params.clone(), self.shadow.clone())
+        self.params.copy_(self.ema)
+        self.refresh_shadows()
+        try:
+            yield
+        finally:
+            self.params.copy_(keep[0])
+            self.shadow.copy_(keep[1])
+            self.wt()
+
+    def _eval_padded(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> tuple:
+        """(x, y, N) on the device, zero-padded to whole batches; cached by the identity of the
+        tensors passed (and kept with them), so a worker's repeated evaluations copy once."""
+        c = self._eval_cache
+        if c is not None and c[0] is x_u8 and c[1] is y_u8:
+            return c[2], c[3], c[4]
+        hw = self.spec.in_hw
+        y = y_u8.reshape(-1)
+        N = self.E.check_records(int(y.numel()))
+        x = x_u8.reshape(N, hw, hw, 3)
+        rows = (N + self.batch - 1) // self.batch * self.batch
+        xp = torch.zeros(rows, hw, hw, 3, dtype=torch.uint8, device=self.device)
+        yp = torch.zeros(rows, dtype=torch.uint8, device=self.device)
+        xp[:N].copy_(x)
+        yp[:N].copy_(y)
+        self._eval_cache = (x_u8, y_u8, xp, yp, N)
+        return xp, yp, N
+
+    def evaluate_full(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False, topk: int = 5):
+        """The held-out report (EvalReport) over EVERY record of (x, y), running statistics as in
+        :meth:`evaluate`.  The set is padded with zero records to whole batches; per batch one
+        ``forward_eval``, one ``sl_eval_accum`` launch that counts the batch's first ``n_valid`` rows into
+        a 264-word integer block on the device, and the cursor bump.  The host waits once, for the block
+        after the last batch: nothing in the loop reads the device.  Eval-mode BatchNorm normalises each
+        row with the running statistics, so the padding rows cannot reach the valid ones.  ``ema=True``
+        as in :meth:`evaluate`; training state, cursor and running statistics are bit-identical
+        afterwards and no tensor moves, so a captured graph stays valid.  Between steps only."""
+        E = self.E
+        topk = E.check_topk(topk, self.spec.classes)
+        if ema:
+            with self._ema_weights():
+                return self.evaluate_full(x_u8, y_u8, topk=topk)
+        x, y, N = self._eval_padded(x_u8, y_u8)
+        B = self.batch
+        acc = E.new_acc(self.device)
+        saved = (self.x, self.y, self.cursor)
+        self.x, self.y, self.cursor = x, y, torch.zeros(1, dtype=torch.int32, device=self.device)
+        try:
+            for b in range(x.shape[0] // B):
+                self.forward_eval()
+                E.eval_accum(self.logits, self.labels, self.loss, min(B, N - b * B), self.spec.classes, topk, acc)
+                self.K.cursor_bump(self.cursor)
+        finally:
+            self.x, self.y, self.cursor = saved
+        return E.report_from_acc(acc, self.spec.classes, topk)

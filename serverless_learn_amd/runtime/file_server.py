@@ -12,6 +12,8 @@ Here:
   records (:mod:`serverless_learn_amd.data.synthetic`), generated on first
   request and cached; with ``dataset="reference-dummy"`` file 0 is the
   reference's dummy file byte for byte (C++ ``reference_dummy_file``);
+* file ``EVAL_BASE`` (with ``eval_every > 0``) is the held-out validation shard: ``eval_records``
+  records of the same task drawn with ``eval_seed``, generated and cached like a data shard;
 * files ``>= CKPT_BASE`` are checkpoints uploaded with the additive
   ``FileStore.StoreFile`` RPC (optionally persisted to ``store_dir``);
 * an unknown file yields ``PushOutcome{ok=false}`` -- never an exit;
@@ -27,7 +29,7 @@ import threading
 import time
 
 from ..config import Config
-from ..ckpt.format import CKPT_BASE
+from ..ckpt.format import CKPT_BASE, EVAL_BASE
 from ..data.synthetic import make_shard
 from ..proto import messages as pb
 from ..utils.log import Logger
@@ -84,7 +86,8 @@ class FileServer:
             data = self._files.get(file_num)
             if data is not None:
                 return data
-            if file_num >= CKPT_BASE or file_num >= self._num_shards():
+            held_out = file_num == EVAL_BASE and self.cfg.eval_every > 0  # the validation shard
+            if not held_out and (file_num >= CKPT_BASE or file_num >= self._num_shards()):
                 return None
             if self.cfg.dataset == "reference-dummy" and file_num != 0:
                 return None
@@ -94,7 +97,12 @@ class FileServer:
                 if file_num in self._files:
                     return self._files[file_num]
             t0 = time.perf_counter()
-            if self.cfg.dataset == "reference-dummy":
+            if held_out:
+                # the same task (the class prototypes do not depend on the seed), records of another
+                # seed: disjoint from every training shard
+                data = make_shard(self.cfg.eval_records, shard_index=0, num_shards=1, seed=self.cfg.held_out_seed,
+                                  dataset=self.cfg.dataset)
+            elif self.cfg.dataset == "reference-dummy":
                 from .._core import core
 
                 data = core().reference_dummy_file(self.cfg.dummy_file_length)

@@ -30,7 +30,7 @@ import time
 from concurrent import futures
 
 from .._core import core
-from ..ckpt.format import CKPT_BASE
+from ..ckpt.format import CKPT_BASE, EVAL_BASE
 from ..config import Config
 from ..parallel.ps import PS_CLIENT_MD, ParameterServer
 from ..proto import messages as pb
@@ -41,6 +41,9 @@ from .transport import Channels, RpcFailure, RpcServer, metadata_dict
 
 # FlowFeedback's step-time breakdown fields (proto fields 11-16)
 PHASE_FIELDS = ("step_ms", "data_wait_ms", "compute_ms", "exchange_ms", "update_ms", "exchange_gbps")
+# ... and its held-out evaluation fields (17-23), present once a worker has evaluated
+EVAL_FIELDS = ("eval_step", "eval_loss", "eval_accuracy", "eval_topk_accuracy", "eval_samples", "eval_ema_loss",
+               "eval_ema_accuracy")
 
 
 def _free_port() -> int:
@@ -64,6 +67,7 @@ class Master:
         self.incarnation: dict[str, int] = {}
         self.delivered: dict[str, tuple] = {}       # addr -> (incarnation, file_num)
         self.ckpt_delivered: dict[str, tuple] = {}  # addr -> (incarnation, ckpt file)
+        self.eval_delivered: dict[str, int] = {}    # addr -> incarnation that holds the held-out shard (eval_every > 0)
         self.latest_ckpt = 0
         self.feedback: dict[str, dict] = {}
         self._job_logged = 0.0
@@ -105,6 +109,7 @@ class Master:
             with self._lock:
                 self.delivered.pop(info.addr, None)
                 self.ckpt_delivered.pop(info.addr, None)
+                self.eval_delivered.pop(info.addr, None)
             self.ps.client_left(info.addr)
         self.log.info("deregister", worker=info.addr, existed=existed, epoch=self.registry.epoch(),
                       world=len(self.registry.members()))
@@ -164,6 +169,8 @@ class Master:
                                        "group_samples_per_sec": fb.group_samples_per_sec,
                                        "group_loss": fb.group_loss, "group_world": fb.group_world,
                                        **{k: getattr(fb, k) for k in PHASE_FIELDS}}
+                if fb.eval_step:  # held-out evaluation (fields 17-23; zero until the first one)
+                    self.feedback[addr].update({k: getattr(fb, k) for k in EVAL_FIELDS})
         except RpcFailure as e:
             evicted = self.registry.heartbeat_fail(addr, self.cfg.max_misses)
             self.log.warn("checkup_failed", worker=addr, evicted=evicted, error=e.code.name if e.code else "")
@@ -172,6 +179,7 @@ class Master:
                 with self._lock:
                     self.delivered.pop(addr, None)
                     self.ckpt_delivered.pop(addr, None)
+                    self.eval_delivered.pop(addr, None)
                     self.feedback.pop(addr, None)
                 self.ps.client_left(addr)
                 self.log.info("evicted", worker=addr, epoch=self.registry.epoch(), world=len(self.registry.members()))
@@ -215,8 +223,19 @@ class Master:
         phases = {k: round(sum(f.get(k, 0.0) for f in live) / len(live), 4) for k in PHASE_FIELDS} if live else {}
         if live:
             phases["max_step_ms"] = round(max(f["step_ms"] for f in live), 4)
-        return {"samples_per_sec": round(sum(groups.values()) + solo, 1), "groups": len(groups),
-                "workers": len(fb), "phases": phases}
+        job = {"samples_per_sec": round(sum(groups.values()) + solo, 1), "groups": len(groups),
+               "workers": len(fb), "phases": phases}
+        # held-out evaluation: the newest report any worker holds (a group's members evaluate the same
+        # set with identical replicas and report identical figures: one of them stands for the group)
+        ev = max((f for f in fb.values() if f.get("eval_step", 0) > 0), key=lambda f: f["eval_step"], default=None)
+        if ev is not None:
+            job["eval"] = {"step": ev["eval_step"], "loss": round(ev["eval_loss"], 6),
+                           "accuracy": round(ev["eval_accuracy"], 6),
+                           "topk_accuracy": round(ev["eval_topk_accuracy"], 6), "samples": ev["eval_samples"]}
+            if ev["eval_ema_loss"] or ev["eval_ema_accuracy"]:  # the weight EMA's report (zero: none)
+                job["eval"].update(ema_loss=round(ev["eval_ema_loss"], 6),
+                                   ema_accuracy=round(ev["eval_ema_accuracy"], 6))
+        return job
 
     # ---- push scheduling -------------------------------------------------------
     def _num_shards(self, n_members: int) -> int:
@@ -241,6 +260,7 @@ class Master:
             ckpt = self.latest_ckpt
             need_ckpt = ckpt and self.ckpt_delivered.get(addr) != (inc, ckpt) and self.delivered.get(addr) is None
             need_data = (self.cfg.push_policy == "periodic") or self.delivered.get(addr) != (inc, shard)
+            need_eval = self.cfg.eval_every > 0 and self.eval_delivered.get(addr) != inc
         if need_ckpt:  # a fresh incarnation resumes from the newest checkpoint first
             if self._request_push(addr, ckpt):
                 with self._lock:
@@ -248,6 +268,10 @@ class Master:
         if need_data and self._request_push(addr, shard):
             with self._lock:
                 self.delivered[addr] = (inc, shard)
+        if need_eval and self._request_push(addr, EVAL_BASE):
+            # the held-out shard, once per worker incarnation (a failed push is tried again next round)
+            with self._lock:
+                self.eval_delivered[addr] = inc
 
     def push_once(self) -> None:
         n = len(self.registry)

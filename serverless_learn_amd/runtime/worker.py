@@ -22,7 +22,10 @@ Here a worker:
   ``gossip`` (exact reference exchange, random peer, never % 0), ``ps`` (the
   master's parameter server) or ``none``;
 * answers ``CheckUp`` with real feedback (step, samples/s, loss, bytes, epoch)
-  and checkpoints to the file server every ``checkpoint_every`` steps (rank 0).
+  and checkpoints to the file server every ``checkpoint_every`` steps (rank 0);
+* with ``eval_every > 0`` keeps the held-out shard the master has pushed (file ``EVAL_BASE``) beside
+  its training shard and evaluates on it every ``eval_every`` steps, between chunks
+  (``trainer.evaluate_full``; the ``eval`` event, the ``sl_eval_*`` gauges, FlowFeedback 17-23).
 """
 from __future__ import annotations
 
@@ -126,6 +129,10 @@ class Worker:
         self._last_checkup = time.monotonic()
         self.has_data = threading.Event()
         self._pending_shard = None
+        # held-out evaluation (eval_every > 0): the validation shard (x, y, file_num) once it has
+        # arrived, and the newest report's figures for the feedback
+        self._eval_shard = None
+        self.eval_last: dict = {}
         self._stop = threading.Event()
         self._threads: list[threading.Thread] = []
         dev_index = self.device.index if self.device.type == "cuda" else -1
@@ -251,10 +258,16 @@ class Worker:
                 buf = torch.from_numpy(buf)
             x = buf[HEADER_SIZE:HEADER_SIZE + n * d].view(n, d)
             y = buf[HEADER_SIZE + n * d:HEADER_SIZE + n * d + n]
-            with self.train_lock:
-                self._pending_shard = (x, y, file_num)
-            self.has_data.set()
-            kind = "shard"
+            if ckfmt.EVAL_BASE <= file_num < ckfmt.CKPT_BASE:
+                # a held-out shard: kept beside the training shard, never trained on (no has_data)
+                with self.train_lock:
+                    self._eval_shard = (x, y, file_num)
+                kind = "eval_shard"
+            else:
+                with self.train_lock:
+                    self._pending_shard = (x, y, file_num)
+                self.has_data.set()
+                kind = "shard"
         elif ckfmt.looks_like_checkpoint(buf[:8].tobytes() if isinstance(buf, np.ndarray) else b""):
             self._load_checkpoint(buf.tobytes())
             kind = "checkpoint"
@@ -281,7 +294,7 @@ class Worker:
                              bytes_ingested=self.bytes_ingested, epoch=self.group.epoch if self.group.epoch >= 0 else 0,
                              state=self.state, group_samples_per_sec=gm["samples_per_sec"],
                              group_loss=gm["loss"], group_accuracy=gm["accuracy"], group_world=gm["world"],
-                             **self.phase_stats)
+                             **self.phase_stats, **self.eval_last)
         return fb.SerializeToString()
 
     def _exchange_updates(self, request: bytes, context) -> bytes:
@@ -861,7 +874,7 @@ class Worker:
                 want = min(want, hold - self.step)
             # chunks end on log / checkpoint boundaries, so every member of a lock-step group
             # runs its group collectives (metrics) at the same step
-            for every in (self.cfg.log_every, self.cfg.checkpoint_every):
+            for every in (self.cfg.log_every, self.cfg.checkpoint_every, self.cfg.eval_every):
                 if every:
                     want = min(want, every - self.step % every)
             prev = self.step
@@ -942,9 +955,45 @@ class Worker:
                     self.save_checkpoint()
                 except Exception as e:
                     self.log.warn("checkpoint_failed", error=repr(e))
+            if self.cfg.eval_every and self.step // self.cfg.eval_every != prev // self.cfg.eval_every:
+                self._evaluate_held_out()
             if self.cfg.max_steps and self.step >= self.cfg.max_steps:
                 self.state = "done"
                 return
+
+    def _evaluate_held_out(self) -> None:
+        """One pass over the validation shard at an ``eval_every`` boundary, between chunks (training
+        pauses for it): the trainer's ``evaluate_full`` of the live weights and, with a weight EMA, of
+        the average.  Every member of a group evaluates the whole set -- replicas are identical, so
+        the figures agree.  Never stops training: no shard yet is an ``eval_skipped`` event, an
+        exception an ``eval_failed`` one."""
+        with self.train_lock:
+            shard = self._eval_shard
+        if shard is None:
+            self.log.info("eval_skipped", step=self.step, reason="no held-out shard yet")
+            return
+        x, y, _ = shard
+        t0 = time.perf_counter()
+        try:
+            with self.train_lock:
+                rep = self.trainer.evaluate_full(x, y, topk=self.cfg.eval_topk)
+                ema = (self.trainer.evaluate_full(x, y, ema=True, topk=self.cfg.eval_topk)
+                       if getattr(self.trainer, "ema", None) is not None else None)
+        except Exception as e:
+            self.log.warn("eval_failed", step=self.step, error=repr(e))
+            return
+        nan0 = lambda v: v if v == v else 0.0  # noqa: E731 (every row bad: the wire carries 0)
+        last = {"eval_step": self.step, "eval_loss": nan0(rep.loss), "eval_accuracy": nan0(rep.accuracy),
+                "eval_topk_accuracy": nan0(rep.topk_accuracy), "eval_samples": rep.n}
+        extra = {}
+        if ema is not None:
+            last.update(eval_ema_loss=nan0(ema.loss), eval_ema_accuracy=nan0(ema.accuracy))
+            extra = {"ema_loss": round(ema.loss, 6), "ema_acc": round(ema.accuracy, 6),
+                     "ema_topk_acc": round(ema.topk_accuracy, 6)}
+        self.eval_last = last
+        self.log.info("eval", step=self.step, loss=round(rep.loss, 6), acc=round(rep.accuracy, 6),
+                      topk_acc=round(rep.topk_accuracy, 6), k=rep.k, n=rep.n, bad=rep.bad,
+                      secs=round(time.perf_counter() - t0, 6), **extra)
 
     def _batch_fields(self) -> dict:
         """The ``train`` event's ``accum_steps`` and ``global_batch``: the samples behind one update

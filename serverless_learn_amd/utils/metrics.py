@@ -14,6 +14,8 @@ numeric fields of a few well-known events feed gauges / counters / histograms:
 * ``train``'s step-time breakdown -> ``sl_step_phase_ms{phase}``, ``sl_exchange_gbps``
 * ``train``'s ``grad_norm`` (gradient clipping on) -> ``sl_grad_norm``
 * ``train``'s ``global_batch`` (``accum_steps * batch * world``) -> ``sl_global_batch``
+* ``eval`` (held-out evaluation) -> ``sl_eval_loss`` / ``sl_eval_accuracy`` / ``sl_eval_topk_accuracy``
+  gauges, ``{role}`` for the live weights and ``{role, weights="ema"}`` for the weight EMA's report
 
 Besides the log events, the transport reports every RPC it serves or makes (SURVEY.md §5.1,
 "per-RPC latency histograms"): ``sl_rpc_seconds{role,side,method,code}`` -- side ``server`` /
@@ -79,6 +81,13 @@ class Metrics:
                                "clipping (reported with gradient clipping on)", ["role"], registry=r)
         self.global_batch = Gauge("sl_global_batch", "samples behind one optimizer step of the whole group "
                                   "(micro-batches per step x per-worker batch x group size)", ["role"], registry=r)
+        # held-out evaluation: weights="" (the label absent) is the live weights' report, "ema" the average's
+        self.eval_loss = Gauge("sl_eval_loss", "mean loss over the held-out shard at the last evaluation",
+                               ["role", "weights"], registry=r)
+        self.eval_acc = Gauge("sl_eval_accuracy", "top-1 accuracy over the held-out shard at the last evaluation",
+                              ["role", "weights"], registry=r)
+        self.eval_topk = Gauge("sl_eval_topk_accuracy", "top-k accuracy over the held-out shard at the last "
+                               "evaluation (k = eval_topk)", ["role", "weights"], registry=r)
 
     # ---- fed by the transport ---------------------------------------------------------
     def rpc(self, side: str, method: str, code: str, seconds: float) -> None:
@@ -126,6 +135,11 @@ class Metrics:
                     self.grad_norm.labels(role).set(fields["grad_norm"])
                 if isinstance(fields.get("global_batch"), (int, float)):
                     self.global_batch.labels(role).set(fields["global_batch"])
+            elif event == "eval":
+                for pre, w in (("", ""), ("ema_", "ema")):
+                    for k, g in (("loss", self.eval_loss), ("acc", self.eval_acc), ("topk_acc", self.eval_topk)):
+                        if isinstance(fields.get(pre + k), (int, float)):
+                            g.labels(role, w).set(fields[pre + k])
             elif event == "job":
                 if isinstance(fields.get("samples_per_sec"), (int, float)):
                     self.job_rate.labels(role).set(fields["samples_per_sec"])
