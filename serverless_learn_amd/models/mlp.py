@@ -21,17 +21,16 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 # (the rules' semantics live there)
-from ..ops.optim import (OptSpec, adamw_update, check_accum_steps, clip_grad_, ema_update_, lr_at,  # noqa: F401
-                         sgd_update)
-from ..utils.graphs import GraphSlots
+from ..ops.optim import (ACCUM_KERNELS, OptSpec, adamw_update, check_accum_steps, clip_grad_,  # noqa: F401
+                         ema_update_, lr_at, sgd_update)
+from ..utils.graphs import GraphedStep
+from .trainer_state import CPUTrainerBase, StepStats, TrainerState  # noqa: F401  (StepStats: imported from here)
 
 D_IN = 784
 D_IN_PAD = 832  # w1h row stride: layer-1 K in 13 chunks of 64 (mlp_fused.hip)
@@ -158,158 +157,20 @@ def reference_grads_bf16(flat: torch.Tensor, x_u8: torch.Tensor, y: torch.Tensor
     return losses.sum(), correct, g
 
 
-class OptStateCPU:
-    """Optimizer state of the CPU trainers beyond ``params`` / ``mom``: AdamW's second moment
-    ``v`` and the optimizer step ``opt_step`` (a 1-element tensor, so a regroup broadcasts it
-    with the rest), both only where the rule needs them; with ``ema_decay > 0`` the averaged
-    parameters ``ema``, their update count ``ema_step`` and the coefficient table ``ema_tab``
-    (ops/optim.py ema_table).  This class is the weight EMA's definition on the trainers."""
-
-    def _init_opt(self, kw: dict) -> None:
-        self.opt = opt = OptSpec(lr=self.lr, momentum=self.momentum, weight_decay=self.weight_decay, **kw)
-        self.mom = torch.zeros_like(self.params) if (self.momentum > 0 or opt.adamw) else None
-        self.v = torch.zeros_like(self.params) if opt.adamw else None
-        self.opt_step = None if opt.plain else torch.zeros(1, dtype=torch.int32)
-        self._grad_norm = None
-        self.ema = self.ema_step = self.ema_tab = None
-        if opt.emas:  # starts at the initial parameters (flat= included)
-            self.ema = self.params.clone()
-            self.ema_step = torch.zeros(1, dtype=torch.int32)
-            self.ema_tab = torch.from_numpy(opt.ema_table())
-
-    def grad_norm(self) -> float | None:
-        """The gradient's global L2 norm at the last step, before clipping (None: clipping off)."""
-        return self._grad_norm
-
-    def _opt_update(self, g: torch.Tensor) -> None:
-        if self.opt.clips:
-            self._grad_norm = clip_grad_(g, self.opt.clip_grad_norm)
-        if self.opt_step is None:
-            sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
-        else:
-            self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]))
-            self.opt_step += 1
-        if self.ema is not None:  # once per update, on the parameters just written
-            t = min(int(self.ema_step[0]), self.ema_tab.numel() - 1)
-            ema_update_(self.ema, self.params, self.ema_tab[t])
-            self.ema_step += 1
-
-    def ema_flat(self) -> torch.Tensor:
-        """A copy of the averaged parameters (``ema_decay > 0``)."""
-        if self.ema is None:
-            raise ValueError("this trainer keeps no weight EMA (ema_decay=0)")
-        return self.ema[:self.n_params].clone()
-
-    def _eval_weights(self, ema: bool) -> torch.Tensor:
-        """What ``evaluate(ema=...)`` runs on: the parameters or their average (only read)."""
-        if ema and self.ema is None:
-            raise ValueError("evaluate(ema=True): this trainer keeps no weight EMA (ema_decay=0)")
-        return self.ema if ema else self.params
-
-    def _opt_state_extra(self, d: dict) -> dict:
-        if self.opt_step is not None:
-            d["opt_step"] = self.opt_step.double().cpu().numpy()
-        if self.v is not None:
-            d["exp_avg_sq"] = self.v[:self.n_params].double().cpu().numpy()
-        if self.ema is not None:
-            d["ema"] = self.ema[:self.n_params].double().cpu().numpy()
-            d["ema_step"] = self.ema_step.double().cpu().numpy()
-        return d
-
-    def _opt_load_state_extra(self, d: dict) -> None:
-        if self.opt_step is not None and "opt_step" in d:
-            self.opt_step.fill_(int(d["opt_step"][0]))
-        if self.v is not None and "exp_avg_sq" in d:
-            self.v[:self.n_params].copy_(torch.as_tensor(np.asarray(d["exp_avg_sq"]), dtype=torch.float32))
-        if self.ema is not None:
-            if "ema" in d and "ema_step" in d:
-                self.ema[:self.n_params].copy_(torch.as_tensor(np.asarray(d["ema"]), dtype=torch.float32))
-                self.ema_step.fill_(int(d["ema_step"][0]))
-            else:  # a checkpoint without one: the average starts over from the weights just loaded
-                self.ema.copy_(self.params)
-                self.ema_step.zero_()
-
-    def _opt_buffers(self) -> list:
-        return [t for t in (self.v, self.opt_step, self.ema, self.ema_step) if t is not None]
-
-    def reset_optimizer_state(self) -> None:
-        for t in (self.mom, self.v, self.opt_step):
-            if t is not None:
-                t.zero_()
-
-    # ---- gradient accumulation: the definition the GPU engines are tested against ----
-    accum_steps = 1
-    grad = None  # the aggregated gradient of the last step, as the optimizer took it
-
-    def set_accum(self, k) -> None:
-        """``k`` micro-batches per optimizer step (one exchange, one clip, one update)."""
-        self.accum_steps = check_accum_steps(k)
-
-    @property
-    def samples_per_step(self) -> int:
-        return self.batch * self.accum_steps
-
-    @property
-    def grad_scale(self) -> float:
-        """The gradient is a mean over the global batch ``batch * world_size * accum_steps``."""
-        return 1.0 / (self.batch * self.world_size * self.accum_steps)
-
-    def _accumulate(self, micro) -> tuple:
-        """(loss_sum, correct_sum, g) of one step: ``micro()`` returns them for the micro-batch at
-        ``self.cursor``, already scaled by :attr:`grad_scale`; the cursor is bumped between them
-        (the step bumps it after the last, with the update), and the micro-gradients are summed in
-        fp32 in order, ``((g_0 + g_1) + g_2) + ...``."""
-        loss, correct, g = micro()
-        for _ in range(1, self.accum_steps):
-            self.cursor += 1
-            li, ci, gi = micro()
-            loss, correct, g = loss + li, correct + ci, g + gi
-        return loss, correct, g
-
-
-@dataclass
-class StepStats:
-    loss: float
-    accuracy: float
-    samples: int
-
-    @property
-    def n(self) -> int:
-        """Samples behind ``loss`` / ``accuracy`` (a training step's: ``accum_steps * batch``)."""
-        return self.samples
-
-
-class CPUTrainer(OptStateCPU):
+class CPUTrainer(CPUTrainerBase):
     """Plain-torch trainer with the same interface as FusedMLPTrainer (CPU workers)."""
 
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 0.0, seed: int = 0, world_size: int = 1,
                  flat: torch.Tensor | None = None, accum_steps: int = 1, **opt):
-        self.batch = batch
-        self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
-        self.world_size = world_size
-        self.set_accum(accum_steps)
-        self.params = (flat if flat is not None else init_params(seed)).clone().float()
-        self._init_opt(opt)  # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (OptSpec)
-        self.cursor = 0
-        self.x = self.y = None
-        self.allreduce = None  # callable(tensor) -> None (sum in place)
-        self._last = None
-        from ..utils.phases import PhaseProbe
-
-        self.phases = PhaseProbe("cpu")
+        self._init_cpu(flat if flat is not None else init_params(seed), batch, lr, momentum, weight_decay,
+                       world_size, accum_steps, opt)
 
     n_params = N_PARAMS
     model_name = "mlp-784-256-256-10"
 
     def layout(self):
         return [[n, list(s), o] for n, s, o, _ in param_layout()]
-
-    def set_world(self, world: int) -> None:
-        self.world_size = world
-
-    def refresh_shadows(self) -> None:
-        pass
 
     def load_shard(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> None:
         assert x_u8.shape[0] >= self.batch
@@ -321,32 +182,6 @@ class CPUTrainer(OptStateCPU):
         xs = self.x[b * self.batch:(b + 1) * self.batch]
         ys = self.y[b * self.batch:(b + 1) * self.batch]
         return reference_grads(self.params, xs, ys, self.grad_scale)
-
-    def step(self) -> None:
-        loss, correct, g = self._accumulate(self._micro)
-        self.phases.mark("compute")
-        if self.allreduce is not None:
-            self.allreduce(g)
-        self.phases.mark("exchange")
-        self.grad = g
-        self._opt_update(g)
-        self.cursor += 1
-        self.phases.mark("update")
-        self._last = (float(loss), float(correct))
-
-    def probe_step(self):
-        """One training step with its phases timed (utils/phases.py; wall clock on the CPU):
-        a PendingPhases, ready at once."""
-        self.phases.arm()
-        self.step()
-        pending = self.phases.finish()
-        pending.exchange_bytes = 4 * int(self.params.numel()) if self.allreduce is not None else 0
-        return pending
-
-    def stats(self) -> StepStats:
-        loss, correct = self._last
-        n = self.samples_per_step
-        return StepStats(loss / n, correct / n, n)
 
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
         """Mean loss / accuracy of the parameters (``ema=True``: of their average) over (x, y)."""
@@ -372,23 +207,6 @@ class CPUTrainer(OptStateCPU):
             rows = F.cross_entropy(logits, torch.where(y < CLASSES, y, 0), reduction="none").float()
         return eval_reference(logits, y, rows, CLASSES, topk)
 
-    def get_flat(self) -> torch.Tensor:
-        return self.params.clone()
-
-    def set_flat(self, flat: torch.Tensor) -> None:
-        self.params.copy_(flat.to(self.params))
-
-    def state_extra(self) -> dict:
-        return self._opt_state_extra({"cursor": np.array([self.cursor], dtype=np.float64)})
-
-    def load_state_extra(self, d: dict) -> None:
-        if "cursor" in d:
-            self.cursor = int(d["cursor"][0])
-        self._opt_load_state_extra(d)
-
-    def buffers(self) -> list:
-        return self._opt_buffers()
-
 
 CPUMLPTrainer = CPUTrainer  # (beside CPUResNetTrainer)
 
@@ -413,7 +231,7 @@ def default_slices(batch: int) -> int:
     return int(_native.lib().sl_mlp_wgrad_slices(batch, 0))
 
 
-class FusedMLPTrainer(GraphSlots):
+class FusedMLPTrainer(GraphedStep, TrainerState):
     """MI355X training engine for the MLP: 3 HIP launches per step.
 
     Buffers are allocated once for a fixed per-GPU batch; the data shard stays
@@ -434,12 +252,6 @@ class FusedMLPTrainer(GraphSlots):
             _native.call("sl_mlp_set_rows_bm", int(os.environ["SL_MLP_ROWS_BM"]))
         dev = torch.device(device)
         self.device = dev
-        self.batch = batch
-        self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
-        self.world_size = world_size
-        # accum_steps micro-batches per optimizer step: the gradient stays a mean over all of them
-        self.accum_steps = check_accum_steps(accum_steps)
-        self.grad_scale = 1.0 / (batch * world_size * self.accum_steps)
         s1 = slices or int(os.environ.get("SL_MLP_WG_SLICES", "0") or 0)  # split-K slices (0: library default)
         self.slices = int(_native.lib().sl_mlp_wgrad_slices(batch, s1))
         if self.slices <= 0:
@@ -450,34 +262,8 @@ class FusedMLPTrainer(GraphSlots):
         self.params = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)
         init = flat if flat is not None else init_params(seed)
         self.params[:n].copy_(init.to(dev))
-        # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
-        self.opt = OptSpec(lr=lr, momentum=momentum, weight_decay=weight_decay, **opt)
-        self.mom = torch.zeros_like(self.params) if (momentum > 0 or self.opt.adamw) else None
-        # AdamW's second moment (mom is its first); the optimizer step the update kernels read
-        # (and its ticket word, mlp_fused.hip opt_end) where the rule depends on the step
-        self.v = torch.zeros_like(self.params) if self.opt.adamw else None
-        self.opt_step = self.opt_ticket = self.lr_tab = None
-        if not self.opt.plain:
-            from ..ops.optim import require_kernels
-
-            require_kernels(self.opt, "sl_mlp_opt", "sl_mlp_opt_xgmi")
-            self.opt_step = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.opt_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._build_lr_table()
-        self.clip_partials = self.clip_norm = None
-        self._init_clip()
-        # the weight EMA (ema_decay > 0): the averaged parameters, the number of EMA updates applied,
-        # the ticket word of the launch that advances it and the coefficient table (ops/optim.py
-        # ema_table); its shadow set for evaluate(ema=True) is allocated on first use
-        self.ema = self.ema_step = self.ema_ticket = self.ema_tab = self._ema_eval = None
-        if self.opt.emas:
-            from ..ops.optim import EMA_KERNELS, require_kernels
-
-            require_kernels(self.opt, *EMA_KERNELS)
-            self.ema = self.params.clone()  # (after flat=)
-            self.ema_step = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.ema_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._build_ema_table()
+        self._init_state(batch, lr, momentum, weight_decay, world_size, accum_steps, opt)
+        self._ema_eval = None  # the EMA's shadow set for evaluate(ema=True), allocated on first use
         bf = torch.bfloat16
         # W1's shadow is fp16: layer 1 multiplies the exact pixels (fp16 1024 + u) and corrects the
         # offset with the W1 row sums, kept as 64-bit fixed-point partials (mlp_fused.hip, R1_BLK)
@@ -502,8 +288,6 @@ class FusedMLPTrainer(GraphSlots):
         self.slab_stride = int(lib.sl_mlp_slab_stride()) if hasattr(lib, "sl_mlp_slab_stride") else self.n_pad
         self.slab = torch.empty(self.slices, self.slab_stride, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)
-        # gradient accumulation's partial sums (gradient, per-sample loss and correct): None at accum_steps 1
-        self.acc = self.loss_acc = self.correct_acc = None
         self._alloc_accum()
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.allreduce = None  # callable(grad_tensor) -> None, sums in place (RCCL)
@@ -511,7 +295,6 @@ class FusedMLPTrainer(GraphSlots):
         self.x = self.y = None
         self.xt = None         # the shard in 64 x 64-byte bricks: what the training launches read
         self.n_batches = 1
-        self.graph = None
         from ..utils.phases import PhaseProbe
 
         self.phases = PhaseProbe(dev)
@@ -523,43 +306,22 @@ class FusedMLPTrainer(GraphSlots):
     n_params = N_PARAMS
     model_name = "mlp-784-256-256-10"
 
+    tickets = ("opt_ticket", "ema_ticket")  # (mlp_fused.hip opt_end; elementwise.hip sl_ema_flat)
+    opt_kernels = ("sl_mlp_opt", "sl_mlp_opt_xgmi")
+    accum_kernels = (*ACCUM_KERNELS, "sl_cursor_bump")
+
     def layout(self):
         return [[n, list(s), o] for n, s, o, _ in param_layout()]
 
-    def set_world(self, world: int) -> None:
-        """Gradient scale follows the group size (mean over the global batch)."""
-        self.world_size = world
-        self.grad_scale = 1.0 / (self.batch * world * self.accum_steps)
-        self.graph = None
-
-    def _alloc_accum(self) -> None:
-        if self.accum_steps == 1:
-            self.acc = self.loss_acc = self.correct_acc = None
-        elif self.acc is None:
-            from ..ops.optim import ACCUM_KERNELS, require_kernels
-
-            require_kernels(self.opt, *ACCUM_KERNELS, "sl_cursor_bump")
-            self.acc = torch.zeros_like(self.grad)
-            self.loss_acc, self.correct_acc = torch.zeros_like(self.loss), torch.zeros_like(self.correct)
-
     def set_accum(self, k: int) -> None:
-        """``k`` micro-batches per optimizer step: each runs rows / wgrad / reduce on its own batch
-        (the cursor moves after each), the reduced gradients are summed in fp32 in order, and the
-        sum takes the exchange hook, the clip and one update.  The gradient scale follows (a mean
-        over ``k * batch * world``); the launches are rebuilt and the captured graphs dropped.
-        Not with the xGMI exchange, which reduces the slab straight into its slot."""
-        k = check_accum_steps(k)
-        if k > 1 and self.xgmi is not None:
+        """:meth:`TrainerState.set_accum`: each micro-batch runs rows / wgrad / reduce, and the sum
+        takes the exchange hook, the clip and one update; the launches are rebuilt and the captured
+        graphs dropped.  Not with the xGMI exchange, which reduces the slab straight into its slot."""
+        if check_accum_steps(k) > 1 and self.xgmi is not None:
             raise ValueError("gradient accumulation is not available with the xGMI exchange "
                              "(keep the process group's all-reduce)")
-        self.accum_steps = k
-        self._alloc_accum()
-        self.set_world(self.world_size)
+        super().set_accum(k)
         self.graph_unrolled = None
-
-    @property
-    def samples_per_step(self) -> int:
-        return self.batch * self.accum_steps
 
     # ---- data ----
     def load_shard(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> None:
@@ -583,11 +345,18 @@ class FusedMLPTrainer(GraphSlots):
         self.graph = None
 
     # ---- kernels ----
-    def refresh_shadows(self) -> None:
+    SHADOWS = ("w1h", "w2h", "w2th", "w3h", "w3th", "r1p")
+
+    def _build_shadows(self, flat: torch.Tensor, s: dict) -> None:
+        """The shadow set ``s`` (:attr:`SHADOWS` by name) of the flat vector ``flat``: the update
+        launch with nothing to apply."""
         n = self._n
-        n.call("sl_mlp_sgd", n.ptr(self.params), None, None, 0, 0, None, None, 0.0, 0.0, 0.0, self.xa, self.xb, 0,
-               n.ptr(self.w1h), n.ptr(self.w2h), n.ptr(self.w2th), n.ptr(self.w3h), n.ptr(self.w3th),
-               None, n.ptr(self.r1p), n.stream_ptr())
+        n.call("sl_mlp_sgd", n.ptr(flat), None, None, 0, 0, None, None, 0.0, 0.0, 0.0, self.xa, self.xb, 0,
+               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w2th"]), n.ptr(s["w3h"]), n.ptr(s["w3th"]),
+               None, n.ptr(s["r1p"]), n.stream_ptr())
+
+    def refresh_shadows(self) -> None:
+        self._build_shadows(self.params, self._eval_set(False))
 
     @property
     def dh1_scale(self) -> float:
@@ -596,21 +365,6 @@ class FusedMLPTrainer(GraphSlots):
     @property
     def dw1_coeffs(self) -> tuple:
         return dw1_coeffs(self.xa, self.xb, self.dh1_scale)
-
-    def _build_lr_table(self) -> None:
-        tab = self.opt.lr_table()
-        self.lr_tab = torch.from_numpy(tab).to(self.device) if tab is not None else None
-
-    def _build_ema_table(self) -> None:
-        self.ema_tab = torch.from_numpy(self.opt.ema_table()).to(self.device)
-
-    def _init_clip(self) -> None:
-        """Gradient clipping's scratch (the workgroups' fp64 partial sums) and the norm it reports."""
-        if self.opt.clips and self.clip_norm is None:
-            from ..ops.optim import CLIP_KERNELS, clip_buffers, require_kernels
-
-            require_kernels(self.opt, *CLIP_KERNELS)
-            self.clip_partials, self.clip_norm = clip_buffers(N_PARAMS, self.device)
 
     def set_optimizer(self, **kw) -> None:
         """Change optimizer hyper-parameters (OptSpec fields; ``clip_grad_norm`` under any rule,
@@ -630,11 +384,7 @@ class FusedMLPTrainer(GraphSlots):
             raise ValueError("gradient clipping is not available with the xGMI exchange")
         self.opt = new
         self.lr, self.momentum, self.weight_decay = new.lr, new.momentum, new.weight_decay
-        if not new.plain:
-            self._build_lr_table()
-        if new.emas:
-            self._build_ema_table()
-        self._init_clip()
+        self._opt_tables()
         self.graph = None
         self._lkey = None
 
@@ -669,20 +419,21 @@ class FusedMLPTrainer(GraphSlots):
                               p(self.h1t), p(self.dh2t), p(self.dh1t), p(self.w3p), self.w3p.shape[0], p(self.slab),
                               self.slices, self.slab_stride, entry="sl_mlp_wgrad" + sfx),
         }
-        for name, (mode, from_grad, grad_out, bump) in {"sgd": (2, False, False, True),
-                                                        "reduce": (1, False, True, False),
-                                                        "update": (2, True, False, True)}.items():
-            if mode == 2 and not self.opt.plain:  # the update under a step-counter rule (reduce: rule-independent)
+        # the update kernel's three forms: the fused "sgd" (the slab reduced and applied), the "reduce"
+        # of the slab into grad (rule-independent; no cursor bump) and the "update" from grad
+        for name, from_grad in (("sgd", False), ("reduce", False), ("update", True)):
+            slab, gin = (None, p(self.grad)) if from_grad else (p(self.slab), None)
+            reduce = name == "reduce"
+            if not reduce and not self.opt.plain:  # under a step-counter rule
                 lc[name] = n.Launch("sl_mlp_opt", self.opt.rule, p(self.params), p(self.mom), p(self.v),
-                                    None if from_grad else p(self.slab), self.slices, self.slab_stride,
-                                    p(self.grad) if from_grad else None, self.lr, self.momentum, self.weight_decay,
-                                    *self.dw1_coeffs, *ws, p(self.cursor), p(self.r1p), *self._opt_args())
+                                    slab, self.slices, self.slab_stride, gin, self.lr, self.momentum,
+                                    self.weight_decay, *self.dw1_coeffs, *ws, p(self.cursor), p(self.r1p),
+                                    *self._opt_args())
                 continue
-            lc[name] = n.Launch("sl_mlp_sgd", p(self.params), p(self.mom),
-                                None if from_grad else p(self.slab), self.slices, self.slab_stride,
-                                p(self.grad) if from_grad else None, p(self.grad) if grad_out else None,
-                                self.lr, self.momentum, self.weight_decay, *self.dw1_coeffs, mode, *ws,
-                                p(self.cursor) if bump else None, p(self.r1p))
+            lc[name] = n.Launch("sl_mlp_sgd", p(self.params), p(self.mom), slab, self.slices, self.slab_stride,
+                                gin, p(self.grad) if reduce else None, self.lr, self.momentum, self.weight_decay,
+                                *self.dw1_coeffs, 1 if reduce else 2, *ws, None if reduce else p(self.cursor),
+                                p(self.r1p))
         if self.opt.clips:  # between the reduce and the update launches, on the real parameters only
             lc["clip"] = n.Launch("sl_clip_grad_norm", p(self.grad), N_PARAMS, self.opt.clip_grad_norm,
                                   p(self.clip_partials), self.clip_partials.numel(), p(self.clip_norm))
@@ -722,37 +473,40 @@ class FusedMLPTrainer(GraphSlots):
         return (p(self.opt_step), p(self.opt_ticket), p(self.lr_tab),
                 self.lr_tab.numel() if self.lr_tab is not None else 0, *self.opt.adam_scalars())
 
+    def _eval_rows(self, s: dict, x, y, rows: int, loss=None, correct=None, logits=None, cursor=None,
+                   n_batches: int = 1) -> None:
+        """The evaluation-form rows launch (forward only) on the weight set ``s`` (:meth:`_eval_set`):
+        ``rows`` rows of (x, y) -- batch ``cursor % n_batches`` of them with a device cursor -- into
+        whichever of the per-row ``loss`` / ``correct`` and the ``logits`` are given."""
+        n = self._n
+        p = n.ptr
+        n.call("sl_mlp_rows", p(x), p(y), p(cursor), n_batches, rows,
+               p(s["w1h"]), p(s["w2h"]), p(s["w3h"]), p(s["w2th"]), p(s["w3th"]),
+               p(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
+               p(loss), p(correct), p(logits), 0, p(s["r1p"]), None, n.stream_ptr())
+
     def _rows(self, train: bool = True):
         if train:
             return self._launches()["rows"]()
-        n = self._n
-        n.call("sl_mlp_rows", n.ptr(self.x), n.ptr(self.y), n.ptr(self.cursor), self.n_batches, self.batch,
-               n.ptr(self.w1h), n.ptr(self.w2h), n.ptr(self.w3h), n.ptr(self.w2th), n.ptr(self.w3th),
-               n.ptr(self.params), self.xa, self.xb, self.grad_scale, self.dh1_scale,
-               n.ptr(self.h1t), n.ptr(self.w3p), n.ptr(self.dh2t), n.ptr(self.dh1t),
-               n.ptr(self.loss), n.ptr(self.correct), None, 0, n.ptr(self.r1p), None, n.stream_ptr())
+        self._eval_rows(self._eval_set(False), self.x, self.y, self.batch, self.loss, self.correct,
+                        cursor=self.cursor, n_batches=self.n_batches)
 
     def _wgrad(self):
         self._launches()["wgrad"]()
 
     def _sgd(self, mode: int, from_grad: bool, grad_out: bool, bump: bool = True):
-        name = {(2, False, False, True): "sgd", (1, False, True, False): "reduce",
-                (2, True, False, True): "update"}[(mode, from_grad, grad_out, bump)]
-        self._launches()[name]()
+        """(tests, scripts) An update-kernel launch by its form: "reduce" writes the gradient out,
+        "update" reads it, "sgd" does neither."""
+        self._launches()["reduce" if grad_out else "update" if from_grad else "sgd"]()
 
     def compute_grads(self) -> torch.Tensor:
         """Forward + backward only; returns the reduced (local) gradient (not with an xGMI
         exchange enabled: its rows launch advances the exchange's step id)."""
-        self._rows(True)
-        self._wgrad()
-        self._sgd(1, from_grad=False, grad_out=True, bump=False)
+        lc = self._launches()
+        lc["rows"]()
+        lc["wgrad"]()
+        lc["reduce"]()
         return self.grad[:N_PARAMS]
-
-    def step(self) -> None:
-        if self.graph is not None:
-            self.graph.replay()
-            return
-        self._step_eager()
 
     def steps(self, n: int) -> None:
         """Run ``n`` full training steps.  With a multi-step graph captured
@@ -809,62 +563,41 @@ class FusedMLPTrainer(GraphSlots):
         return out
 
     def _step_eager(self) -> None:
+        """One step.  Of ``accum_steps`` > 1 micro-batches: grad = ((g_0 + g_1) + ...) + g_last, then
+        the reduce -> hook -> clip -> update path of a clipping step (no fused slab update)."""
         if getattr(self, "probe", None) is not None:
             self.probe()
-        ph = self.phases
-        if self.accum_steps > 1:
-            return self._step_accum()
-        self._rows(True)
-        self._wgrad()
+        lc, ph, last = self._launches(), self.phases, self.accum_steps - 1
+        for i in range(last + 1):
+            lc["rows"]()
+            lc["wgrad"]()
+            if last:
+                lc["reduce"]()
+                for launch in lc["acc_fold" if i == last else "acc_add" if i else "acc_store"]:
+                    launch()
+                if i < last:
+                    lc["bump"]()
         ph.mark("compute")
-        if self.xgmi is not None:
-            lc = self._launches()
+        if self.xgmi is not None:  # (never with accumulation)
             lc["xreduce"]()
             for launch in lc["xbarrier"]:
                 launch()
             ph.mark("exchange")  # slab reduction into the exchange slot + the step barrier(s)
             lc["xupdate"]()      # (the peers' slots are summed inside the update kernel)
-        elif self.allreduce is None and not self.opt.clips:
-            self._sgd(2, from_grad=False, grad_out=False)
+        elif self.allreduce is None and not self.opt.clips and not last:
+            lc["sgd"]()
         else:
-            self._sgd(1, from_grad=False, grad_out=True, bump=False)
+            if not last:
+                lc["reduce"]()
             if self.allreduce is not None:
                 self.allreduce(self.grad)
                 ph.mark("exchange")
             if self.opt.clips:  # the whole norm before any weight moves: the fused slab update cannot clip
-                self._launches()["clip"]()
-            self._sgd(2, from_grad=True, grad_out=False)
+                lc["clip"]()
+            lc["update"]()
         if self.ema is not None:  # local, so also behind the xGMI update
-            self._launches()["ema"]()
-        ph.mark("update")
-
-    def _step_accum(self) -> None:
-        """One step of ``accum_steps`` micro-batches: grad = ((g_0 + g_1) + ...) + g_last, then the
-        reduce -> hook -> clip -> update path of a clipping step (no fused slab update)."""
-        lc, ph, last = self._launches(), self.phases, self.accum_steps - 1
-        for i in range(last + 1):
-            lc["rows"]()
-            lc["wgrad"]()
-            lc["reduce"]()
-            for launch in lc["acc_fold" if i == last else "acc_add" if i else "acc_store"]:
-                launch()
-            if i < last:
-                lc["bump"]()
-        ph.mark("compute")
-        if self.allreduce is not None:
-            self.allreduce(self.grad)
-            ph.mark("exchange")
-        if self.opt.clips:
-            lc["clip"]()
-        lc["update"]()
-        if self.ema is not None:
             lc["ema"]()
         ph.mark("update")
-
-    def grad_norm(self) -> float | None:
-        """The aggregated gradient's global L2 norm at the last step, before clipping (one float
-        read from the device); None with clipping off."""
-        return float(self.clip_norm[0]) if self.opt.clips else None
 
     def probe_step(self):
         """One eager training step with its phase boundaries recorded (utils/phases.py): returns
@@ -876,39 +609,12 @@ class FusedMLPTrainer(GraphSlots):
         pending.exchange_bytes = 4 * N_PARAMS if (self.allreduce is not None or self.xgmi is not None) else 0
         return pending
 
-    def drop_graphs(self) -> None:
-        """Release every captured step graph after the device has finished with them.  A
-        graph may hold a communicator's kernels: the runtime calls this before it re-forms or
-        tears down the group, so no replay is in flight when the old
-        communicator goes away and the k-step graph is not left alive holding it."""
-        if self.graph is not None or self.retired_graphs:  # steps() ignores graph_unrolled once graph is None (ADVICE r05)
-            torch.cuda.synchronize(self.device)
-        self.graph = None
-        self.graph_unrolled = None
-        self.reap_graphs(sync=False)
-
     def capture(self, warmup: int = 2, unroll: int = 1) -> None:
-        """Capture one step into a hipGraph (kernels only, or kernels + RCCL);
-        ``unroll > 1`` also captures a k-step graph used by :meth:`steps`.  Graphs replaced
-        since the last capture are freed first, after a device sync (utils/graphs.py)."""
-        self.reap_graphs()
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._step_eager()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._step_eager()
-        self.graph = g
+        """:meth:`GraphedStep.capture`; ``unroll > 1`` also captures a k-step graph used by :meth:`steps`."""
+        super().capture(warmup)
         self.graph_unrolled, self.unroll = None, max(1, int(unroll))
         if self.unroll > 1:
-            gk = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gk):
-                for _ in range(self.unroll):
-                    self._step_eager()
-            self.graph_unrolled = gk
+            self.graph_unrolled = self._capture_steps(self.unroll)
 
     # ---- eval / state ----
     def w1_out_of_range(self) -> bool:
@@ -924,59 +630,41 @@ class FusedMLPTrainer(GraphSlots):
         n = self.samples_per_step  # (an accumulated step leaves the sums over its micro-batches in loss / correct)
         return StepStats(loss / n, acc / n, n)
 
-    def ema_flat(self) -> torch.Tensor:
-        """A copy of the averaged parameters (``ema_decay > 0``)."""
-        if self.ema is None:
-            raise ValueError("this trainer keeps no weight EMA (ema_decay=0)")
-        return self.ema[:N_PARAMS].clone()
-
     def _eval_set(self, ema: bool) -> dict:
         """The weights an evaluation launch reads: the training set, or with ``ema`` a second set
         of shadows (allocated on first use) rebuilt from the averaged parameters by the launch that
         ``refresh_shadows`` uses -- what a second trainer holds after ``set_flat(ema_flat())``.  No
         training tensor is written or moved, so a captured graph stays valid."""
-        names = ("w1h", "w2h", "w2th", "w3h", "w3th", "r1p")
         if not ema:
-            return dict({k: getattr(self, k) for k in names}, params=self.params)
+            return dict({k: getattr(self, k) for k in self.SHADOWS}, params=self.params)
         if self.ema is None:
             raise ValueError("ema=True: this trainer keeps no weight EMA (ema_decay=0)")
         if self._ema_eval is None:
-            self._ema_eval = {k: torch.zeros_like(getattr(self, k)) for k in names}
-        s, n = self._ema_eval, self._n
-        n.call("sl_mlp_sgd", n.ptr(self.ema), None, None, 0, 0, None, None, 0.0, 0.0, 0.0, self.xa, self.xb, 0,
-               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w2th"]), n.ptr(s["w3h"]), n.ptr(s["w3th"]),
-               None, n.ptr(s["r1p"]), n.stream_ptr())
-        return dict(s, params=self.ema)
+            self._ema_eval = {k: torch.zeros_like(getattr(self, k)) for k in self.SHADOWS}
+        self._build_shadows(self.ema, self._ema_eval)
+        return dict(self._ema_eval, params=self.ema)
 
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
         """Mean loss / accuracy over the whole 64-row blocks of (x, y); ``ema=True``: of the
         averaged parameters, the training state untouched (between steps)."""
-        n = self._n
         s = self._eval_set(ema)
         x = x_u8.reshape(-1, D_IN).to(self.device).contiguous()
         y = y_u8.reshape(-1).to(self.device).to(torch.uint8).contiguous()
         rows = x.shape[0] // BLOCK_ROWS * BLOCK_ROWS
         loss = torch.zeros(rows, device=self.device)
         corr = torch.zeros(rows, device=self.device)
-        n.call("sl_mlp_rows", n.ptr(x), n.ptr(y), None, 1, rows,
-               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w3h"]), n.ptr(s["w2th"]), n.ptr(s["w3th"]),
-               n.ptr(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
-               n.ptr(loss), n.ptr(corr), None, 0, n.ptr(s["r1p"]), None, n.stream_ptr())
+        self._eval_rows(s, x, y, rows, loss, corr)
         lv = float("nan") if int(s["r1p"].max()) >= R1_OVF_MIN else float(loss.mean())
         return StepStats(lv, float(corr.mean()), rows)
 
     def logits(self, x_u8: torch.Tensor, ema: bool = False) -> torch.Tensor:
-        n = self._n
         s = self._eval_set(ema)
         x = x_u8.reshape(-1, D_IN).to(self.device).contiguous()
         rows = x.shape[0]
         if rows % BLOCK_ROWS:
             raise ValueError(f"rows must be a multiple of {BLOCK_ROWS}")
         out = torch.empty(rows, CLASSES, device=self.device)
-        n.call("sl_mlp_rows", n.ptr(x), None, None, 1, rows,
-               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w3h"]), n.ptr(s["w2th"]), n.ptr(s["w3th"]),
-               n.ptr(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
-               None, None, n.ptr(out), 0, n.ptr(s["r1p"]), None, n.stream_ptr())
+        self._eval_rows(s, x, None, rows, logits=out)
         if int(s["r1p"].max()) >= R1_OVF_MIN:
             out.fill_(float("nan"))
         return out
@@ -990,7 +678,6 @@ class FusedMLPTrainer(GraphSlots):
         makes every row bad and the loss NaN."""
         from ..ops import evalmetrics as E
 
-        n = self._n
         topk = E.check_topk(topk, CLASSES)
         y = y_u8.reshape(-1)
         N = E.check_records(int(y.numel()))
@@ -1004,10 +691,7 @@ class FusedMLPTrainer(GraphSlots):
         loss = torch.empty(rows, device=self.device)
         out = torch.empty(rows, CLASSES, device=self.device)
         acc = E.new_acc(self.device)
-        n.call("sl_mlp_rows", n.ptr(xp), n.ptr(yp), None, 1, rows,
-               n.ptr(s["w1h"]), n.ptr(s["w2h"]), n.ptr(s["w3h"]), n.ptr(s["w2th"]), n.ptr(s["w3th"]),
-               n.ptr(s["params"]), self.xa, self.xb, 1.0, 1.0, None, None, None, None,
-               n.ptr(loss), None, n.ptr(out), 0, n.ptr(s["r1p"]), None, n.stream_ptr())
+        self._eval_rows(s, xp, yp, rows, loss, logits=out)
         E.eval_accum(out, yp, loss, N, CLASSES, topk, acc)
         rep = E.report_from_acc(acc, CLASSES, topk)
         return rep.all_bad() if int(s["r1p"].max()) >= R1_OVF_MIN else rep
@@ -1018,45 +702,3 @@ class FusedMLPTrainer(GraphSlots):
     def set_flat(self, flat: torch.Tensor) -> None:
         self.params[:N_PARAMS].copy_(flat.to(self.params))
         self.refresh_shadows()
-
-    # ---- exact-resume state beyond the flat vectors (ckpt format v2) ----
-    def state_extra(self) -> dict:
-        """The device batch cursor: a resumed run continues with the batch the saved run
-        would have taken next, so save-at-k + resume + m steps equals k + m steps."""
-        d = {"cursor": self.cursor.double().cpu().numpy()}
-        if self.opt_step is not None:  # the optimizer step and AdamW's second moment (the first
-            d["opt_step"] = self.opt_step.double().cpu().numpy()  # travels as the momentum section)
-        if self.v is not None:
-            d["exp_avg_sq"] = self.v[:N_PARAMS].double().cpu().numpy()
-        if self.ema is not None:  # the averaged parameters and the number of EMA updates behind them
-            d["ema"] = self.ema[:N_PARAMS].double().cpu().numpy()
-            d["ema_step"] = self.ema_step.double().cpu().numpy()
-        return d
-
-    def load_state_extra(self, d: dict) -> None:
-        if "cursor" in d:
-            self.cursor.fill_(int(d["cursor"][0]))
-        if self.opt_step is not None:
-            if "opt_step" in d:
-                self.opt_step.fill_(int(d["opt_step"][0]))
-            self.opt_ticket.zero_()
-        if self.v is not None and "exp_avg_sq" in d:
-            self.v[:N_PARAMS].copy_(torch.as_tensor(np.asarray(d["exp_avg_sq"]), dtype=torch.float32))
-        if self.ema is not None:
-            if "ema" in d and "ema_step" in d:
-                self.ema[:N_PARAMS].copy_(torch.as_tensor(np.asarray(d["ema"]), dtype=torch.float32))
-                self.ema_step.fill_(int(d["ema_step"][0]))
-            else:  # a checkpoint without one: the average starts over from the weights just loaded
-                self.ema.copy_(self.params)
-                self.ema_step.zero_()
-            self.ema_ticket.zero_()
-
-    def buffers(self) -> list:
-        """Optimizer state beyond params / mom (and the weight EMA), broadcast with them after a
-        regroup."""
-        return [t for t in (self.v, self.opt_step, self.ema, self.ema_step) if t is not None]
-
-    def reset_optimizer_state(self) -> None:
-        for t in (self.mom, self.v, self.opt_step, self.opt_ticket):
-            if t is not None:
-                t.zero_()

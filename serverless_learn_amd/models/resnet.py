@@ -28,7 +28,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .mlp import OptStateCPU
+from .trainer_state import CPUTrainerBase, StepStats
 
 ALIGN = 64
 CIFAR_MEAN = (0.4914, 0.4822, 0.4465)
@@ -247,7 +247,45 @@ def ref_grads(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, y: torch
     return losses.detach().sum(), correct.detach(), w.grad.detach()
 
 
-class CPUResNetTrainer(OptStateCPU):
+class ResNetModel:
+    """What the two ResNet trainers add to the shared state (``self.spec``: the ResNetSpec): the
+    model's description, and the BatchNorm running statistics (``running_stats()``: name -> (mean,
+    var)) in the checkpoint and among ``buffers()``, ahead of the optimizer's.  The statistics are
+    not averaged by the weight EMA: they already are a moving average."""
+
+    @property
+    def n_params(self) -> int:
+        return self.spec.n_flat
+
+    @property
+    def model_name(self) -> str:
+        return f"resnet18-{self.spec.stem}"
+
+    def layout(self):
+        return spec_layout(self.spec)
+
+    def _model_extra(self) -> dict:
+        d = {}
+        for name, (rm, rv) in self.running_stats().items():
+            d[f"bn/{name}/mean"] = rm.double().cpu().numpy()
+            d[f"bn/{name}/var"] = rv.double().cpu().numpy()
+        return d
+
+    def load_state_extra(self, d: dict) -> None:
+        for name, (rm, rv) in self.running_stats().items():
+            if f"bn/{name}/mean" in d:
+                rm.copy_(torch.as_tensor(np.asarray(d[f"bn/{name}/mean"]), dtype=torch.float32))
+                rv.copy_(torch.as_tensor(np.asarray(d[f"bn/{name}/var"]), dtype=torch.float32))
+        super().load_state_extra(d)
+
+    def buffers(self) -> list:
+        """Broadcast with the parameters after a regroup, so every replica evaluates identically
+        (each rank's statistics come from its own batches); the optimizer state beyond params / mom
+        and the weight EMA likewise."""
+        return [t for pair in self.running_stats().values() for t in pair] + super().buffers()
+
+
+class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
     """Plain-torch trainer with FusedResNetTrainer's interface (CPU workers, tests)."""
 
     def __init__(self, batch: int, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 5e-4,
@@ -256,7 +294,6 @@ class CPUResNetTrainer(OptStateCPU):
                  label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
                  accum_steps: int = 1, **opt):
         from ..data import augment as A
-        from .mlp import StepStats, sgd_update  # noqa: F401
 
         self.spec = resnet18_spec(stem, 10, in_hw)
         A.check(augment, augment_pad, self.spec.in_hw)
@@ -270,37 +307,12 @@ class CPUResNetTrainer(OptStateCPU):
         # that stats() reports is against each sample's own label: a diagnostic
         self.label_smoothing, self.mixup_alpha, self.cutmix_alpha = label_smoothing, mixup_alpha, cutmix_alpha
         self.last_mix = None
-        self.batch = batch
-        self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
-        self.world_size = world_size
-        self.set_accum(accum_steps)
-        self.params = (flat if flat is not None else init_params(self.spec, seed)).clone().float()
-        self._init_opt(opt)  # optimizer=, beta1=, ..., lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
+        self._init_cpu(flat if flat is not None else init_params(self.spec, seed), batch, lr, momentum,
+                       weight_decay, world_size, accum_steps, opt)
         self.running = running_stats(self.spec)
-        self.x = self.y = None
-        self.cursor = 0
-        self.allreduce = None
-        self._last = None
-        from ..utils.phases import PhaseProbe
 
-        self.phases = PhaseProbe("cpu")
-
-    @property
-    def n_params(self) -> int:
-        return self.spec.n_flat
-
-    @property
-    def model_name(self) -> str:
-        return f"resnet18-{self.spec.stem}"
-
-    def layout(self):
-        return spec_layout(self.spec)
-
-    def set_world(self, world: int) -> None:
-        self.world_size = world
-
-    def refresh_shadows(self) -> None:
-        pass
+    def running_stats(self) -> dict:
+        return self.running
 
     def load_shard(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> None:
         hw = self.spec.in_hw
@@ -334,66 +346,9 @@ class CPUResNetTrainer(OptStateCPU):
                                                       self.spec.classes))
         return ref_grads(self.spec, self.params, xs, ys, self.grad_scale, self.running, targets)
 
-    def step(self) -> None:
-        loss, correct, g = self._accumulate(self._micro)
-        self.phases.mark("compute")
-        if self.allreduce is not None:
-            self.allreduce(g)
-        self.phases.mark("exchange")
-        self.grad = g
-        self._opt_update(g)
-        self.cursor += 1
-        self.phases.mark("update")
-        self._last = (float(loss), float(correct))
-
-    def probe_step(self):
-        """One training step with its phases timed (utils/phases.py; wall clock on the CPU):
-        a PendingPhases, ready at once."""
-        self.phases.arm()
-        self.step()
-        pending = self.phases.finish()
-        pending.exchange_bytes = 4 * int(self.params.numel()) if self.allreduce is not None else 0
-        return pending
-
-    def stats(self):
-        from .mlp import StepStats
-
-        loss, correct = self._last
-        n = self.samples_per_step
-        return StepStats(loss / n, correct / n, n)
-
-    def get_flat(self) -> torch.Tensor:
-        return self.params.clone()
-
-    def set_flat(self, flat: torch.Tensor) -> None:
-        self.params.copy_(flat.to(self.params))
-
-    # ---- exact-resume state beyond the flat vectors (ckpt format v2) ----
-    def state_extra(self) -> dict:
-        d = {"cursor": np.array([self.cursor], dtype=np.float64)}
-        for name, (rm, rv) in self.running.items():
-            d[f"bn/{name}/mean"] = rm.double().numpy()
-            d[f"bn/{name}/var"] = rv.double().numpy()
-        return self._opt_state_extra(d)
-
-    def load_state_extra(self, d: dict) -> None:
-        if "cursor" in d:
-            self.cursor = int(d["cursor"][0])
-        for name, (rm, rv) in self.running.items():
-            if f"bn/{name}/mean" in d:
-                rm.copy_(torch.from_numpy(np.asarray(d[f"bn/{name}/mean"])).to(rm.dtype))
-                rv.copy_(torch.from_numpy(np.asarray(d[f"bn/{name}/var"])).to(rv.dtype))
-        self._opt_load_state_extra(d)
-
-    def buffers(self) -> list:
-        """Non-parameter state every replica must agree on (broadcast after a regroup)."""
-        return [t for pair in self.running.values() for t in pair] + self._opt_buffers()
-
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False):
         """Inference with the BatchNorm running statistics (eval mode); ``ema=True``: of the averaged
         parameters, with the same running statistics (those are not averaged)."""
-        from .mlp import StepStats
-
         with torch.no_grad():
             logits = ref_forward(self.spec, self._eval_weights(ema), x_u8.reshape(-1, self.spec.in_hw, self.spec.in_hw, 3),
                                  False, self.running)

@@ -39,9 +39,9 @@ import contextlib
 import os
 import torch
 
-from ..utils.graphs import GraphSlots
-from .mlp import StepStats
-from .resnet import CIFAR_MEAN, CIFAR_STD, BlockSpec, BNSpec, ConvSpec, init_params, resnet18_spec
+from ..utils.graphs import GraphedStep
+from .resnet import CIFAR_MEAN, CIFAR_STD, BlockSpec, BNSpec, ConvSpec, ResNetModel, init_params, resnet18_spec
+from .trainer_state import StepStats, TrainerState
 
 LOGIT_LD = 16  # dlogits row stride (classes padded for 16-B gathers)
 
@@ -79,7 +79,10 @@ class _Conv:
         self.wt = torch.zeros(spec.cin * spec.k * spec.k * self.ldt, dtype=torch.bfloat16, device=dev)
 
 
-class FusedResNetTrainer(GraphSlots):
+class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
+    tickets = ("ema_ticket",)  # (the update launches read opt_step; a cursor_bump advances it)
+    opt_kernels = ("sl_adamw_flat", "sl_sgd_flat_lr")
+
     def __init__(self, batch: int, device="cuda", lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 5e-4, seed: int = 0, world_size: int = 1, stem: str = "cifar",
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
@@ -105,12 +108,7 @@ class FusedResNetTrainer(GraphSlots):
         self.label_smoothing, self.mixup_alpha, self.cutmix_alpha = label_smoothing, mixup_alpha, cutmix_alpha
         self.mixes = mixup_alpha > 0 or cutmix_alpha > 0
         dev = self.device = torch.device(device)
-        self.batch = B = batch
-        self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
-        self.world_size = world_size
-        # accum_steps micro-batches per optimizer step: the gradient stays a mean over all of them
-        self.accum_steps = O.check_accum_steps(accum_steps)
-        self.grad_scale = 1.0 / (batch * world_size * self.accum_steps)
+        B = batch
         self.bn_momentum = bn_momentum
         self.shortcut_even_on = os.environ.get("SL_SHORTCUT_EVEN", "1") != "0"
         # BN-on-load: where the direct 3x3 kernel serves a block's conv2 (64 channels, 32 wide), it
@@ -120,35 +118,9 @@ class FusedResNetTrainer(GraphSlots):
         n = spec.n_flat
         self.params = torch.zeros(n, dtype=torch.float32, device=dev)
         self.params.copy_((flat if flat is not None else init_params(spec, seed)).to(dev))
-        # optimizer=, beta1=, beta2=, adam_eps=, lr_schedule=, lr_warmup_steps=, ... (ops.optim.OptSpec)
-        self.opt = O.OptSpec(lr=lr, momentum=momentum, weight_decay=weight_decay, **opt)
-        self.mom = torch.zeros_like(self.params) if (momentum > 0 or self.opt.adamw) else None
-        # AdamW's second moment (mom is its first) and the device-resident optimizer step the
-        # update kernel reads, where the rule depends on the step
-        self.v = torch.zeros_like(self.params) if self.opt.adamw else None
-        self.opt_step = self.lr_tab = None
-        if not self.opt.plain:
-            O.require_kernels(self.opt, "sl_adamw_flat", "sl_sgd_flat_lr")
-            self.opt_step = torch.zeros(1, dtype=torch.int32, device=dev)
-            tab = self.opt.lr_table()
-            self.lr_tab = torch.from_numpy(tab).to(dev) if tab is not None else None
+        self._init_state(batch, lr, momentum, weight_decay, world_size, accum_steps, opt)
         self.grad = torch.zeros_like(self.params)
-        # gradient clipping: the workgroups' fp64 partial sums and the norm it reports
-        self.clip_partials = self.clip_norm = None
-        if self.opt.clips:
-            O.require_kernels(self.opt, *O.CLIP_KERNELS)
-            self.clip_partials, self.clip_norm = O.clip_buffers(n, dev)
         self.shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
-        # the weight EMA (ema_decay > 0): the averaged parameters, the number of EMA updates applied,
-        # the ticket word of the launch that advances it and the coefficient table (ops/optim.py
-        # ema_table).  BatchNorm running statistics are not averaged: they already are a moving average
-        self.ema = self.ema_step = self.ema_ticket = self.ema_tab = None
-        if self.opt.emas:
-            O.require_kernels(self.opt, *O.EMA_KERNELS)
-            self.ema = self.params.clone()  # (after flat=)
-            self.ema_step = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.ema_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.ema_tab = torch.from_numpy(self.opt.ema_table()).to(dev)
         bns = list(spec.bns())
         rsz = {b.name: (K.rsum_floats(2 * b.c) + 3) // 4 * 4 for b in bns}  # 16-B aligned regions
         self.arena = torch.zeros(sum(2 * rsz[b.name] for b in bns), device=dev)
@@ -229,12 +201,9 @@ class FusedResNetTrainer(GraphSlots):
         self.dlogits = torch.zeros(B, 1, 1, LOGIT_LD, **bf)
         self.loss = torch.zeros(B, device=dev)
         self.correct = torch.zeros(B, device=dev)
-        # gradient accumulation's partial sums (gradient, per-sample loss and correct): None at accum_steps 1
-        self.acc = self.loss_acc = self.correct_acc = None
         self._alloc_accum()
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.x = self.y = None
-        self.graph = None
         self.bucket_hook = None   # callable(flat_view) -> handle, launched during backward
         self.bucket_wait = None   # callable(handles) -> None, before the optimizer
         from ..utils.phases import PhaseProbe
@@ -266,46 +235,6 @@ class FusedResNetTrainer(GraphSlots):
         d, c1 = blk.down, blk.conv1
         return (self.shortcut_even_on and d is not None and d.k == 1 and d.stride == 2 and d.pad == 0
                 and c1.k == 3 and c1.stride == 2 and c1.pad == 1 and d.cout % 64 == 0 and c1.cout % 64 == 0)
-
-    @property
-    def n_params(self) -> int:
-        return self.spec.n_flat
-
-    @property
-    def model_name(self) -> str:
-        return f"resnet18-{self.spec.stem}"
-
-    def layout(self):
-        from .resnet import spec_layout
-
-        return spec_layout(self.spec)
-
-    def set_world(self, world: int) -> None:
-        self.world_size = world
-        self.grad_scale = 1.0 / (self.batch * world * self.accum_steps)
-        self.graph = None
-
-    def _alloc_accum(self) -> None:
-        if self.accum_steps == 1:
-            self.acc = self.loss_acc = self.correct_acc = None
-        elif self.acc is None:
-            self.O.require_kernels(self.opt, *self.O.ACCUM_KERNELS)
-            self.acc = torch.zeros_like(self.grad)
-            self.loss_acc, self.correct_acc = torch.zeros_like(self.loss), torch.zeros_like(self.correct)
-
-    def set_accum(self, k: int) -> None:
-        """``k`` micro-batches per optimizer step: each runs forward and backward on its own batch
-        (own input-pipeline draws, own BatchNorm statistics; the cursor moves after each), the
-        gradients are summed in fp32 in order, and the sum takes the bucket hooks / all-reduce,
-        the clip and one update.  The gradient scale follows (a mean over ``k * batch * world``)
-        and the captured graph is dropped."""
-        self.accum_steps = self.O.check_accum_steps(k)
-        self._alloc_accum()
-        self.set_world(self.world_size)
-
-    @property
-    def samples_per_step(self) -> int:
-        return self.batch * self.accum_steps
 
     # ------------------------------------------------------------------
     def refresh_shadows(self) -> None:
@@ -564,17 +493,6 @@ class FusedResNetTrainer(GraphSlots):
                           self.weight_decay, shadow=self.shadow)
         self.K.cursor_bump(self.opt_step)
 
-    def grad_norm(self) -> float | None:
-        """The aggregated gradient's global L2 norm at the last step, before clipping (one float
-        read from the device); None with clipping off."""
-        return float(self.clip_norm[0]) if self.opt.clips else None
-
-    def step(self) -> None:
-        if self.graph is not None:
-            self.graph.replay()
-            return
-        self._step_eager()
-
     def probe_step(self):
         """One eager training step with its phase boundaries recorded (utils/phases.py): returns
         a PendingPhases, resolved by the caller once the device has finished the step."""
@@ -584,27 +502,6 @@ class FusedResNetTrainer(GraphSlots):
         hooked = self.allreduce is not None or self.bucket_hook is not None
         pending.exchange_bytes = 4 * int(self.grad.numel()) if hooked else 0
         return pending
-
-    def drop_graphs(self) -> None:
-        """Release the captured step graph once the device is done with it (called by the
-        runtime before it re-forms or tears down a group whose collectives the graph holds)."""
-        if self.graph is not None or self.retired_graphs:
-            torch.cuda.synchronize(self.device)
-        self.graph = None
-        self.reap_graphs(sync=False)
-
-    def capture(self, warmup: int = 2) -> None:
-        self.reap_graphs()  # graphs replaced since the last capture, freed after a sync (utils/graphs.py)
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._step_eager()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._step_eager()
-        self.graph = g
 
     # ------------------------------------------------------------------
     def compute_grads(self) -> torch.Tensor:
@@ -625,61 +522,8 @@ class FusedResNetTrainer(GraphSlots):
         self.params.copy_(flat.to(self.params))
         self.refresh_shadows()
 
-    def ema_flat(self) -> torch.Tensor:
-        """A copy of the averaged parameters (``ema_decay > 0``)."""
-        if self.ema is None:
-            raise ValueError("this trainer keeps no weight EMA (ema_decay=0)")
-        return self.ema.clone()
-
     def running_stats(self) -> dict:
         return {name: (b.run_mean, b.run_var) for name, b in self.bn.items()}
-
-    # ---- exact-resume state beyond the flat vectors (ckpt format v2) ----
-    def state_extra(self) -> dict:
-        d = {"cursor": self.cursor.double().cpu().numpy()}
-        for name, b in self.bn.items():
-            d[f"bn/{name}/mean"] = b.run_mean.double().cpu().numpy()
-            d[f"bn/{name}/var"] = b.run_var.double().cpu().numpy()
-        if self.opt_step is not None:  # the optimizer step and AdamW's second moment (the first
-            d["opt_step"] = self.opt_step.double().cpu().numpy()  # travels as the momentum section)
-        if self.v is not None:
-            d["exp_avg_sq"] = self.v.double().cpu().numpy()
-        if self.ema is not None:  # the averaged parameters and the number of EMA updates behind them
-            d["ema"] = self.ema.double().cpu().numpy()
-            d["ema_step"] = self.ema_step.double().cpu().numpy()
-        return d
-
-    def load_state_extra(self, d: dict) -> None:
-        if "cursor" in d:
-            self.cursor.fill_(int(d["cursor"][0]))
-        for name, b in self.bn.items():
-            if f"bn/{name}/mean" in d:
-                b.run_mean.copy_(torch.as_tensor(d[f"bn/{name}/mean"], dtype=torch.float32))
-                b.run_var.copy_(torch.as_tensor(d[f"bn/{name}/var"], dtype=torch.float32))
-        if self.opt_step is not None and "opt_step" in d:
-            self.opt_step.fill_(int(d["opt_step"][0]))
-        if self.v is not None and "exp_avg_sq" in d:
-            self.v.copy_(torch.as_tensor(d["exp_avg_sq"], dtype=torch.float32))
-        if self.ema is not None:
-            if "ema" in d and "ema_step" in d:
-                self.ema.copy_(torch.as_tensor(d["ema"], dtype=torch.float32))
-                self.ema_step.fill_(int(d["ema_step"][0]))
-            else:  # a checkpoint without one: the average starts over from the weights just loaded
-                self.ema.copy_(self.params)
-                self.ema_step.zero_()
-            self.ema_ticket.zero_()
-
-    def buffers(self) -> list:
-        """BN running statistics: broadcast with the parameters after a regroup, so every
-        replica evaluates identically (each rank's statistics come from its own batches); the
-        optimizer state beyond params / mom and the weight EMA likewise."""
-        bufs = [t for b in self.bn.values() for t in (b.run_mean, b.run_var)]
-        return bufs + [t for t in (self.v, self.opt_step, self.ema, self.ema_step) if t is not None]
-
-    def reset_optimizer_state(self) -> None:
-        for t in (self.mom, self.v, self.opt_step):
-            if t is not None:
-                t.zero_()
 
     # ---- inference with running statistics ----
     def _eval_coef(self, bn: _BN, eps: float = 1e-5) -> torch.Tensor:
@@ -716,50 +560,11 @@ class FusedResNetTrainer(GraphSlots):
         K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
                      None, self.grad_scale)
 
-    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
-        """Eval-mode loss / accuracy over every whole batch of (x, y) with the running
-        statistics; the training shard, cursor and statistics are left untouched.  ``ema=True``:
-        of the averaged parameters, with the same running statistics -- what a second trainer
-        returns after ``set_flat(ema_flat())``.  The parameters' contents are swapped for the
-        average's and put back (with the bf16 shadow; the transposed weights are rebuilt from it), so
-        no tensor moves and a captured graph stays valid.  Between steps only."""
-        if ema:
-            if self.ema is None:
-                raise ValueError("evaluate(ema=True): this trainer keeps no weight EMA (ema_decay=0)")
-            keep = (self.params.clone(), self.shadow.clone())
-            self.params.copy_(self.ema)
-            self.refresh_shadows()
-            try:
-                return self.evaluate(x_u8, y_u8)
-            finally:
-                self.params.copy_(keep[0])
-                self.shadow.copy_(keep[1])
-                self.wt()
-        hw = self.spec.in_hw
-        x = x_u8.reshape(-1, hw, hw, 3).to(self.device).contiguous()
-        y = y_u8.reshape(-1).to(self.device).to(torch.uint8).contiguous()
-        nb = x.shape[0] // self.batch
-        if nb < 1:
-            raise ValueError("evaluation set smaller than one batch")
-        saved = (self.x, self.y, self.cursor)
-        self.x, self.y, self.cursor = x, y, torch.zeros(1, dtype=torch.int32, device=self.device)
-        loss = corr = 0.0
-        try:
-            for _ in range(nb):
-                self.forward_eval()
-                loss += float(self.loss.sum())
-                corr += float(self.correct.sum())
-                self.K.cursor_bump(self.cursor)
-        finally:
-            self.x, self.y, self.cursor = saved
-        n = nb * self.batch
-        return StepStats(loss / n, corr / n, n)
-
-    # ---- the held-out evaluation pass (ops/evalmetrics.py) ----
     @contextlib.contextmanager
     def _ema_weights(self):
-        """:meth:`evaluate`'s ``ema=True`` swap: the parameters' contents become the average's and are
-        put back (with the bf16 shadow; the transposed weights are rebuilt from it).  No tensor moves."""
+        """``ema=True`` of the evaluations: the parameters' contents become the average's and are put
+        back (with the bf16 shadow; the transposed weights are rebuilt from it).  No tensor moves, so
+        a captured graph stays valid."""
         if self.ema is None:
             raise ValueError("evaluate(ema=True): this trainer keeps no weight EMA (ema_decay=0)")
         keep = (self.params.clone(), self.shadow.clone())
@@ -772,6 +577,42 @@ class FusedResNetTrainer(GraphSlots):
             self.shadow.copy_(keep[1])
             self.wt()
 
+    @contextlib.contextmanager
+    def _eval_shard(self, x: torch.Tensor, y: torch.Tensor):
+        """(x, y) on the device as the current shard, read from batch 0 on by a cursor of its own; the
+        training shard and cursor are put back untouched."""
+        saved = (self.x, self.y, self.cursor)
+        self.x, self.y, self.cursor = x, y, torch.zeros(1, dtype=torch.int32, device=self.device)
+        try:
+            yield
+        finally:
+            self.x, self.y, self.cursor = saved
+
+    def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False) -> StepStats:
+        """Eval-mode loss / accuracy over every whole batch of (x, y) with the running
+        statistics; the training shard, cursor and statistics are left untouched.  ``ema=True``:
+        of the averaged parameters, with the same running statistics -- what a second trainer
+        returns after ``set_flat(ema_flat())`` (:meth:`_ema_weights`).  Between steps only."""
+        if ema:
+            with self._ema_weights():
+                return self.evaluate(x_u8, y_u8)
+        hw = self.spec.in_hw
+        x = x_u8.reshape(-1, hw, hw, 3).to(self.device).contiguous()
+        y = y_u8.reshape(-1).to(self.device).to(torch.uint8).contiguous()
+        nb = x.shape[0] // self.batch
+        if nb < 1:
+            raise ValueError("evaluation set smaller than one batch")
+        loss = corr = 0.0
+        with self._eval_shard(x, y):
+            for _ in range(nb):
+                self.forward_eval()
+                loss += float(self.loss.sum())
+                corr += float(self.correct.sum())
+                self.K.cursor_bump(self.cursor)
+        n = nb * self.batch
+        return StepStats(loss / n, corr / n, n)
+
+    # ---- the held-out evaluation pass (ops/evalmetrics.py) ----
     def _eval_padded(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> tuple:
         """(x, y, N) on the device, zero-padded to whole batches; cached by the identity of the
         tensors passed (and kept with them), so a worker's repeated evaluations copy once."""
@@ -807,13 +648,9 @@ class FusedResNetTrainer(GraphSlots):
         x, y, N = self._eval_padded(x_u8, y_u8)
         B = self.batch
         acc = E.new_acc(self.device)
-        saved = (self.x, self.y, self.cursor)
-        self.x, self.y, self.cursor = x, y, torch.zeros(1, dtype=torch.int32, device=self.device)
-        try:
+        with self._eval_shard(x, y):
             for b in range(x.shape[0] // B):
                 self.forward_eval()
                 E.eval_accum(self.logits, self.labels, self.loss, min(B, N - b * B), self.spec.classes, topk, acc)
                 self.K.cursor_bump(self.cursor)
-        finally:
-            self.x, self.y, self.cursor = saved
         return E.report_from_acc(acc, self.spec.classes, topk)

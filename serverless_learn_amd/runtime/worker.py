@@ -348,7 +348,7 @@ class Worker:
             if mom is not None and self.trainer.mom is not None:
                 self.trainer.mom[:self.trainer.n_params].copy_(torch.from_numpy(mom))
             ema_missing = getattr(self.trainer, "ema", None) is not None and not {"ema", "ema_step"} <= set(extra)
-            if (extra or ema_missing) and hasattr(self.trainer, "load_state_extra"):
+            if extra or ema_missing:
                 # batch cursor, BN running statistics, optimizer step, v, the weight EMA (absent from
                 # the file: it starts over from the weights just loaded)
                 self.trainer.load_state_extra(extra)
@@ -369,7 +369,7 @@ class Worker:
             meta = {"model": self.trainer.model_name, "step": self.step, "epoch": self.group.epoch,
                     "layout": self.trainer.layout(),
                     "optimizer": self.trainer.opt.meta()}
-            extra = self.trainer.state_extra() if hasattr(self.trainer, "state_extra") else {}
+            extra = self.trainer.state_extra()
         data = ckfmt.encode(flat, meta, mom, extra)
         file_num = ckfmt.CKPT_BASE + self.ckpt_slot
         self.ckpt_slot ^= 1  # two alternating slots: never overwrite one being served
@@ -941,7 +941,7 @@ class Worker:
                     # replica checksum for the elastic rehearsal (scripts/elastic_demo.py): a float64
                     # copy of every parameter and a device sync, so opt-in only
                     extra["param_sum"] = float(self.trainer.params.double().sum())
-                gn = self.trainer.grad_norm() if hasattr(self.trainer, "grad_norm") else None
+                gn = self.trainer.grad_norm()
                 if gn is not None:  # gradient clipping on: the last step's norm before clipping
                     extra["grad_norm"] = round(gn, 6)
                 self.log.info("train", step=self.step, loss=round(st.loss, 4), acc=round(st.accuracy, 4),
@@ -1004,7 +1004,7 @@ class Worker:
 
     def _samples_per_step(self) -> int:
         """Samples this worker consumes per optimizer step: ``accum_steps * batch``."""
-        return getattr(self.trainer, "samples_per_step", self.trainer.batch)
+        return self.trainer.samples_per_step
 
     def _idle(self, secs: float, event: threading.Event | None = None) -> None:
         """A wait of the training loop (no data, waiting for the group or a peer's data):

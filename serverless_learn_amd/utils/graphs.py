@@ -53,3 +53,44 @@ class GraphSlots:
         if sync and self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         retired.clear()
+
+
+class GraphedStep(GraphSlots):
+    """A fused trainer's ``step`` over its ``_step_eager``: eager, or the replay of a captured graph."""
+
+    def step(self) -> None:
+        if self.graph is not None:
+            self.graph.replay()
+            return
+        self._step_eager()
+
+    def _capture_steps(self, k: int = 1):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(k):
+                self._step_eager()
+        return g
+
+    def capture(self, warmup: int = 2) -> None:
+        """Capture one step into a hipGraph (kernels only, or kernels + RCCL), after ``warmup`` eager
+        steps on a side stream.  Graphs replaced since the last capture are freed first, after a
+        device sync (module doc)."""
+        self.reap_graphs()
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._step_eager()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self.graph = self._capture_steps()
+
+    def drop_graphs(self) -> None:
+        """Release every captured step graph after the device has finished with them.  A
+        graph may hold a communicator's kernels: the runtime calls this before it re-forms or
+        tears down the group, so no replay is in flight when the old
+        communicator goes away and the k-step graph is not left alive holding it."""
+        if self.graph is not None or self.retired_graphs:  # steps() ignores graph_unrolled once graph is None (ADVICE r05)
+            torch.cuda.synchronize(self.device)
+        self.graph = None
+        self.graph_unrolled = None
+        self.reap_graphs(sync=False)

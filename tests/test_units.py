@@ -563,7 +563,7 @@ def test_worker_chunk_failure_counts_completed_steps_and_releases_lock(monkeypat
         return out[0]
 
     class Failing(_FakeGraphTrainer):
-        batch = 8
+        batch = samples_per_step = 8
 
         def __init__(self, fail_at):
             super().__init__()
