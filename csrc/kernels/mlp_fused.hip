@@ -834,9 +834,13 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
     const float s = quarters_sum((e[0] + e[1]) + (e[2] + e[3]));
     const float zl = quarters_sum((zs[0] + zs[1]) + (zs[2] + zs[3]));
     const int idx = quarters_min(min(min(ix[0], ix[1]), min(ix[2], ix[3])));
-    const float lse = mx + __logf(s);
+    // loss = lse - z_label with lse = mx + log s, formed as (mx - z_label) + log s: the difference of
+    // two logits first (small next to them where the label is among the largest, and exact where the
+    // logits are integers), so the one rounding that matters is at the loss's own magnitude.  mx + log s
+    // first would round at the magnitude of mx, and the difference again.
+    const float gap = mx - zl;
     if (lg == 0) {  // 16 consecutive rows per store instruction
-      if (a.loss) a.loss[row0 + row] = lse - zl;
+      if (a.loss) a.loss[row0 + row] = gap + __logf(s);
       if (a.correct) a.correct[row0 + row] = (idx == lab) ? 1.f : 0.f;
     }
     if (a.logits) {
