@@ -843,6 +843,167 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------
+// Softmax cross-entropy over 17..256 classes: the narrow kernel's formulas with one row on a whole
+// wave.  Lane c owns the four adjacent classes 4c .. 4c + 3, so 64 lanes cover 256 classes; the
+// lane's logits are one 16-B load where every row starts on a 16-B boundary (VEC: ncls % 4 == 0)
+// and four guarded dword loads otherwise; its four dz values leave as one 8-B store (ldd is a power
+// of two >= 32, so lanes 4c < ldd cover exactly columns [0, ldd) and columns [ncls, ldd) get
+// zeros).  Maximum, sum, first-maximum index and sum_c q_c z_c are 64-lane butterflies, whose
+// result is the same bits in every lane.  A wave takes rows_per_wave consecutive rows and keeps its
+// four bias-gradient partial sums in registers.
+//
+// Bias gradient, with no float atomic and no SL_DETERMINISTIC branch: the four waves of a workgroup
+// are added through LDS in wave order, the workgroup stores one partial row ws[blockIdx][ldd], and
+// softmax_ce_wide_fold_kernel (a second, one-workgroup launch) adds the partial rows in workgroup
+// order into dbias.  Grid and order depend on N alone: the same bits from call to call, in both
+// builds.
+constexpr int CEW_WAVES = 4;
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = min(v, __shfl_xor(v, m));
+  return v;
+}
+
+template <bool SOFT, bool VEC>
+__global__ __launch_bounds__(256) void softmax_ce_wide_kernel(const float* __restrict__ z,
+                                                              const uint8_t* __restrict__ lab,
+                                                              float* __restrict__ loss, float* __restrict__ correct,
+                                                              uint16_t* __restrict__ dz, int ldd,
+                                                              float* __restrict__ ws, int N, int ncls,
+                                                              float grad_scale, const int* __restrict__ mix,
+                                                              float eps, int rows_per_wave) {
+  __shared__ float bsum[CEW_WAVES][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c0 = 4 * lane;
+  const int row0 = (blockIdx.x * CEW_WAVES + wave) * rows_per_wave;
+  float bacc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < rows_per_wave; ++i) {
+    const int row = row0 + i;
+    if (row >= N) break;  // (the same for all 64 lanes)
+    const float* zr = z + (long)row * ncls;
+    float v[4];
+    if constexpr (VEC) {
+      // ncls % 4 == 0: a lane's four classes are all inside the row or all outside it
+      if (c0 < ncls) {
+        const float4 t = *reinterpret_cast<const float4*>(zr + c0);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+      } else {
+        v[0] = v[1] = v[2] = v[3] = -INFINITY;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = c0 + j < ncls ? zr[c0 + j] : -INFINITY;
+    }
+    const float mx = wave_max(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+    float e[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) e[j] = c0 + j < ncls ? __expf(v[j] - mx) : 0.f;
+    const float s = wave_sum((e[0] + e[1]) + (e[2] + e[3]));
+    int l = lab[row];
+    l = l < ncls ? l : 0;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    float zl;
+    if constexpr (SOFT) {
+      int lb = l;
+      float wb = 0.f;
+      if (mix) {
+        const int pj = mix[8 * row];
+        lb = (unsigned)pj < (unsigned)N ? lab[pj] : l;
+        lb = lb < ncls ? lb : 0;
+        wb = (float)mix[8 * row + 1] / (float)mix[8 * row + 2];
+      }
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = c0 + j;
+        // classes beyond ncls hold -inf: they take no part in sum_c q_c z_c
+        q[j] = c < ncls ? (1.f - eps) * ((c == l ? 1.f - wb : 0.f) + (c == lb ? wb : 0.f)) + eps / (float)ncls : 0.f;
+        t += c < ncls ? q[j] * v[j] : 0.f;
+      }
+      zl = wave_sum(t);
+    } else {
+      const int j = l & 3;
+      zl = __shfl(j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3], l >> 2);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[k] = c0 + k == l ? 1.f : 0.f;
+    }
+    // the lowest index among the maxima (classes beyond ncls hold -inf but never win: 4 * 64 = 256)
+    int idx = 256;
+#pragma unroll
+    for (int j = 3; j >= 0; --j) idx = (c0 + j < ncls && v[j] == mx) ? c0 + j : idx;
+    idx = wave_min(idx);
+    if (lane == 0) {
+      if (loss) loss[row] = mx + __logf(s) - zl;
+      if (correct) correct[row] = idx == l ? 1.f : 0.f;
+    }
+    float dv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      dv[j] = c0 + j < ncls ? (e[j] / s - q[j]) * grad_scale : 0.f;
+      bacc[j] += dv[j];
+    }
+    if (c0 < ldd) *reinterpret_cast<uint2*>(dz + (long)row * ldd + c0) = make_uint2(pack2(dv[0], dv[1]), pack2(dv[2], dv[3]));
+  }
+  if (!ws) return;  // (a kernel argument: the whole workgroup leaves)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bsum[wave][c0 + j] = bacc[j];
+  __syncthreads();
+  if (tid < ldd) {
+    float acc = bsum[0][tid];
+#pragma unroll
+    for (int w = 1; w < CEW_WAVES; ++w) acc += bsum[w][tid];
+    ws[(long)blockIdx.x * ldd + tid] = acc;
+  }
+}
+
+// dbias[c] += ((ws[0][c] + ws[1][c]) + ...) + ws[parts - 1][c]: one workgroup, workgroup order
+__global__ __launch_bounds__(256) void softmax_ce_wide_fold_kernel(const float* __restrict__ ws, int parts, int ldd,
+                                                                   int ncls, float* __restrict__ dbias) {
+  const int c = threadIdx.x;
+  if (c >= ncls) return;
+  float acc = 0.f;
+  int g = 0;
+  // eight loads in flight at a time, added in workgroup order
+  for (; g + 8 <= parts; g += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = ws[(long)(g + j) * ldd + c];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += v[j];
+  }
+  for (; g < parts; ++g) acc += ws[(long)g * ldd + c];
+  dbias[c] += acc;
+}
+
+// Rows per workgroup of softmax_ce_wide_kernel (a multiple of its four waves; 16 as in the narrow
+// kernel); SL_CE_WIDE_ROWS overrides it for A/B runs (profiles/r18_classes).
+static int ce_wide_rows_per_wave() {
+  static int rows = -1;
+  if (rows < 0) {
+    const char* e = getenv("SL_CE_WIDE_ROWS");
+    const int per_wg = e ? atoi(e) : 16;
+    rows = per_wg >= CEW_WAVES && per_wg <= 256 && per_wg % CEW_WAVES == 0 ? per_wg / CEW_WAVES : 16 / CEW_WAVES;
+  }
+  return rows;
+}
+
+static long ce_wide_parts(int N) {
+  const int per_wg = CEW_WAVES * ce_wide_rows_per_wave();
+  return ((long)N + per_wg - 1) / per_wg;
+}
+
+// ---------------------------------------------------------------------------
 extern "C" int sl_rsum_fold(float* buf, int n, hipStream_t stream);  // conv.hip
 extern "C" int sl_rsum_fold2(float* buf, float* buf2, int n, hipStream_t stream);  // conv.hip
 
@@ -1064,6 +1225,51 @@ int sl_softmax_ce_soft(const float* z, const uint8_t* lab, float* loss, float* c
   hipLaunchKernelGGL((softmax_ce_kernel<true, const int*, float>), dim3((N + 15) / 16), dim3(256), 0, stream, z, lab, loss, correct, dz,
                      ldd, dbias, N, ncls, grad_scale, mix, eps);
   SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// fp32 words of the bias-gradient workspace that sl_softmax_ce_wide needs for N rows at stride ldd
+long sl_softmax_ce_wide_ws_floats(int N, int ldd) { return N < 1 || ldd < 1 ? 0 : ce_wide_parts(N) * ldd; }
+
+// The loss over 17..256 classes (softmax_ce_wide_kernel).  soft = 0: one-hot labels, mix and eps
+// ignored; soft = 1: sl_softmax_ce_soft's targets.  ldd: a power of two with max(32, ncls) <= ldd <=
+// 256 (the FC data gradient reads dz as an ldd-channel image).  ws: caller-owned fp32 workspace of
+// ws_floats >= sl_softmax_ce_wide_ws_floats(N, ldd) words, needed when dbias is given; it holds
+// nothing between calls.  Anything else is refused before any launch.
+int sl_softmax_ce_wide(const float* z, const uint8_t* lab, float* loss, float* correct, uint16_t* dz, int ldd,
+                       float* dbias, int N, int ncls, float grad_scale, const int* mix, float eps, int soft,
+                       float* ws, long ws_floats, hipStream_t stream) {
+  if (ncls < 17 || ncls > 256 || N < 1) return -1;
+  if (ldd < 32 || ldd > 256 || (ldd & (ldd - 1)) || ldd < ncls) return -1;
+  if (soft && !(eps >= 0.f && eps < 1.f)) return -1;
+  if (!z || !lab || !dz || ((uintptr_t)dz & 7)) return -2;
+  const long parts = ce_wide_parts(N);
+  if (dbias && (!ws || ws_floats < parts * ldd)) return -1;
+  if (parts > 0x7fffffffL) return -1;
+  const bool vec = ncls % 4 == 0 && ((uintptr_t)z & 15) == 0;
+  const dim3 grid((unsigned)parts), block(256);
+  float* part = dbias ? ws : nullptr;
+  const int rpw = ce_wide_rows_per_wave();
+  if (soft) {
+    if (vec)
+      hipLaunchKernelGGL((softmax_ce_wide_kernel<true, true>), grid, block, 0, stream, z, lab, loss, correct, dz, ldd,
+                         part, N, ncls, grad_scale, mix, eps, rpw);
+    else
+      hipLaunchKernelGGL((softmax_ce_wide_kernel<true, false>), grid, block, 0, stream, z, lab, loss, correct, dz, ldd,
+                         part, N, ncls, grad_scale, mix, eps, rpw);
+  } else {
+    if (vec)
+      hipLaunchKernelGGL((softmax_ce_wide_kernel<false, true>), grid, block, 0, stream, z, lab, loss, correct, dz, ldd,
+                         part, N, ncls, grad_scale, (const int*)nullptr, 0.f, rpw);
+    else
+      hipLaunchKernelGGL((softmax_ce_wide_kernel<false, false>), grid, block, 0, stream, z, lab, loss, correct, dz,
+                         ldd, part, N, ncls, grad_scale, (const int*)nullptr, 0.f, rpw);
+  }
+  SL_CHECK_LAUNCH();
+  if (dbias) {
+    hipLaunchKernelGGL(softmax_ce_wide_fold_kernel, dim3(1), dim3(256), 0, stream, ws, (int)parts, ldd, ncls, dbias);
+    SL_CHECK_LAUNCH();
+  }
   return 0;
 }
 

@@ -37,7 +37,8 @@ class Config:
     # --- data plane (file_server.cc:40,46) ---
     chunk_size: int = 1_000_000
     dummy_file_length: int = 100_000_000
-    dataset: str = "synthetic-mnist"   # | "synthetic-cifar" | "reference-dummy" (byte-exact reference file 0)
+    dataset: str = "synthetic-mnist"   # | "synthetic-cifar" | "synthetic-cifar100" (100 classes, resnet18) |
+                                       # "reference-dummy" (byte-exact reference file 0)
     shard_records: int = 127_388       # records per shard: a 100,000,000-byte shard
     num_shards: int = 0                # 0 = one shard per worker
     push_policy: str = "on_change"     # "on_change" | "periodic" (reference: re-push every interval)
@@ -55,6 +56,8 @@ class Config:
                                        # largest |m - o| (0 = dense; 0 < x <= 1; not with ps / simulate / compat)
     device: str = "auto"               # auto | cpu | cuda[:N]
     model: str = "mlp"                 # mlp | resnet18 | simulate (reference: vector += 1)
+    classes: int = 0                   # resnet18: outputs of the classifier head (1..256); 0 = the dataset's own
+                                       # count, 10 or synthetic-cifar100's 100.  mlp / simulate: 0 or 10
     batch: int = 1024
     lr: float = 0.05
     momentum: float = 0.9
@@ -117,6 +120,7 @@ class Config:
         the input pipeline's, the soft-target loss's, held-out evaluation's and the top-k sparse
         gossip's)."""
         self._validate_eval()
+        self._validate_classes()
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
         if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:
@@ -155,6 +159,27 @@ class Config:
             raise ValueError("gossip_topk: the simulate model is growable and is never sparse")
         if self.gossip_compat:
             raise ValueError("gossip_topk: gossip_compat reproduces the reference's dense exchange byte for byte")
+
+    def _validate_classes(self) -> None:
+        v = self.classes
+        if isinstance(v, bool) or int(v) != v or not 0 <= v <= 256:
+            raise ValueError(f"classes must be an integer in 0..256 (0 = the dataset's own count), got {v!r}")
+        if self.model in ("mlp", "simulate"):
+            # the MLP rows kernel fuses a 10-wide loss; the simulate model has no classifier
+            if v not in (0, 10):
+                raise ValueError(f"classes={v}: the {self.model} model has ten classes (model='resnet18')")
+            if self.dataset == "synthetic-cifar100":
+                raise ValueError(f"dataset synthetic-cifar100 has 100 classes: the {self.model} model has ten "
+                                 "(model='resnet18')")
+
+    @property
+    def n_classes(self) -> int:
+        """The classifier head's outputs: ``classes``, or with 0 the dataset's own count."""
+        if self.classes:
+            return int(self.classes)
+        from .data.device_synth import dataset_classes
+
+        return dataset_classes(self.dataset)
 
     def _validate_eval(self) -> None:
         def integer(name, lo, hi=None):

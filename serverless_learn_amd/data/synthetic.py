@@ -145,33 +145,37 @@ def make_shard_philox(n: int, shard_index: int = 0, num_shards: int = 1, seed: i
     import os
 
     from .._core import core
-    from .device_synth import KINDS, prototypes
+    from .device_synth import CLASSES, KINDS, dataset_kind, prototypes
 
-    kind = "cifar" if dataset == "synthetic-cifar" else "mnist"
+    kind = dataset_kind(dataset)
+    classes = CLASSES[kind]
     h, w, c, noise, scale, offset = KINDS[kind]
     pixels = h * w * c
     buf = bytearray(HEADER_SIZE + n * pixels + n)
-    buf[:HEADER_SIZE] = HEADER.pack(MAGIC, 1, 1 if c == 1 else 2, n, h, w, 10, shard_index, num_shards,
+    buf[:HEADER_SIZE] = HEADER.pack(MAGIC, 1, 1 if c == 1 else 2, n, h, w, classes, shard_index, num_shards,
                                     c if c > 1 else 0, seed, 0)
     arr = np.frombuffer(buf, dtype=np.uint8)
     images = arr[HEADER_SIZE:HEADER_SIZE + n * pixels]
     labels = arr[HEADER_SIZE + n * pixels:]
     threads = threads or max(1, min(16, (os.cpu_count() or 4)))
-    core().synth_images(images, labels, n, pixels, prototypes(kind), 10, noise, scale, offset,
+    core().synth_images(images, labels, n, pixels, prototypes(kind), classes, noise, scale, offset,
                         seed & ((1 << 64) - 1), shard_index * n, threads)
     return bytes(buf)
 
 
 def make_shard(n: int, shard_index: int = 0, num_shards: int = 1, seed: int = 0, dataset: str = "synthetic-mnist",
                generator: str = "philox") -> bytes:
-    """Shard ``shard_index`` of a seeded synthetic dataset (``synthetic-mnist`` or ``synthetic-cifar``).
+    """Shard ``shard_index`` of a seeded synthetic dataset (``synthetic-mnist``, ``synthetic-cifar`` or the
+    100-class ``synthetic-cifar100``).
 
     ``generator="philox"`` (default): the native multithreaded Philox generator (the K8
     records); ``"numpy"``: the original numpy generator (kept for comparisons and tests)."""
     if generator == "philox":
         return make_shard_philox(n, shard_index, num_shards, seed, dataset)
-    if dataset == "synthetic-cifar":
-        images, labels = make_cifar_like(n, seed=seed * 1000003 + shard_index)
-        return encode_shard(images.reshape(n, -1), labels, shard_index, num_shards, seed, h=32, w=32, channels=3)
+    if dataset in ("synthetic-cifar", "synthetic-cifar100"):
+        classes = 100 if dataset == "synthetic-cifar100" else 10
+        images, labels = make_cifar_like(n, seed=seed * 1000003 + shard_index, classes=classes)
+        return encode_shard(images.reshape(n, -1), labels, shard_index, num_shards, seed, h=32, w=32,
+                            classes=classes, channels=3)
     images, labels = make_mnist_like(n, seed=seed * 1000003 + shard_index)
     return encode_shard(images, labels, shard_index, num_shards, seed)

@@ -43,7 +43,7 @@ from ..utils.graphs import GraphedStep
 from .resnet import CIFAR_MEAN, CIFAR_STD, BlockSpec, BNSpec, ConvSpec, ResNetModel, init_params, resnet18_spec
 from .trainer_state import StepStats, TrainerState
 
-LOGIT_LD = 16  # dlogits row stride (classes padded for 16-B gathers)
+LOGIT_LD = 16  # dlogits row stride up to 16 classes (classes padded for 16-B gathers); above: ops.cnn.logit_ld
 
 
 class _BN:
@@ -95,12 +95,17 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         from ..ops import evalmetrics as E
         from ..ops import optim as O
 
-        self.spec = spec = resnet18_spec(stem, classes, in_hw)
+        # dlogits row stride: LOGIT_LD up to 16 classes (the narrow loss and metrics kernels), else the
+        # next power of two >= max(32, classes) (the wide ones); refuses classes outside 1..256
+        self.logit_ld = K.logit_ld(classes)
+        self.wide = classes > K.NARROW_CLASSES
+        self.spec = spec = resnet18_spec(stem, int(classes), in_hw)
         A.check(augment, augment_pad, spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         _native.lib()
         self.K, self.O, self.E = K, O, E
         self._eval_cache = None  # evaluate_full's padded device copy of the last set passed
+        self._ce_kw = {}  # the loss launch's extra arguments: the wide kernel's workspace (set below)
         # the training input pipeline (data/augment.py): a pure function of (seed, cursor, sample),
         # so the cursor that is checkpointed and broadcast already is all the state it has
         self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
@@ -134,7 +139,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.fc_b = self.params[spec.fc_b:spec.fc_b + classes]
         self.fc_gw = self.grad[spec.fc_w:spec.fc_w + classes * 512]
         self.fc_gb = self.grad[spec.fc_b:spec.fc_b + classes]
-        self.fc_wt = torch.zeros(512 * LOGIT_LD, dtype=torch.bfloat16, device=dev)
+        self.fc_wt = torch.zeros(512 * self.logit_ld, dtype=torch.bfloat16, device=dev)
 
         bf = dict(dtype=torch.bfloat16, device=dev)
         hw = spec.in_hw
@@ -198,7 +203,11 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.dfeat = torch.empty_like(self.feat)
         self.dfeat_in = torch.empty_like(cur)
         self.logits = torch.empty(B, classes, device=dev)
-        self.dlogits = torch.zeros(B, 1, 1, LOGIT_LD, **bf)
+        self.dlogits = torch.zeros(B, 1, 1, self.logit_ld, **bf)
+        # the wide loss's bias-gradient partial rows (None up to 16 classes), allocated once
+        self.ce_ws = K.softmax_ce_wide_ws(B, classes, dev)
+        if self.wide:
+            self._ce_kw = dict(ws=self.ce_ws)
         self.loss = torch.zeros(B, device=dev)
         self.correct = torch.zeros(B, device=dev)
         self._alloc_accum()
@@ -222,7 +231,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
 
         items = [(c.w, c.wt, c.spec.cout, c.spec.k * c.spec.k, c.spec.cin, c.ldt)
                  for c in self.conv.values() if c.spec.name != "stem"]
-        items.append((self.fc_w, self.fc_wt, classes, 1, 512, LOGIT_LD))
+        items.append((self.fc_w, self.fc_wt, classes, 1, 512, self.logit_ld))
         self.wt = K.WeightTransposer(items, dev)
         self.refresh_shadows()
         self.stats()  # load torch's reduction kernel now, not inside the first logged chunk (as mlp.py)
@@ -312,11 +321,12 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             # soft targets; `correct` stays the argmax against the sample's own label (a diagnostic
             # under mixing)
             K.softmax_ce_soft(self.logits, self.labels, self.loss, self.correct,
-                              self.dlogits.view(self.batch, LOGIT_LD), self.fc_gb, self.grad_scale,
-                              mix=self.mix_out, eps=self.label_smoothing)
+                              self.dlogits.view(self.batch, self.logit_ld), self.fc_gb, self.grad_scale,
+                              mix=self.mix_out, eps=self.label_smoothing, **self._ce_kw)
         else:
-            K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
-                         self.fc_gb if train else None, self.grad_scale)
+            K.softmax_ce(self.logits, self.labels, self.loss, self.correct,
+                         self.dlogits.view(self.batch, self.logit_ld), self.fc_gb if train else None,
+                         self.grad_scale, **self._ce_kw)
 
     def backward(self, hook: bool = True, fold: bool = False):
         """``hook=False``: no bucket hook is called (an accumulated step's earlier micro-batches).
@@ -557,8 +567,8 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                 K.bn_apply(st["c2"], co[blk.bn2.name], st["y"], relu=True, res=st["x"])
         K.avgpool_fwd(self.feat_in, self.feat)
         K.conv_fwd(self.feat, self.fc_w, spec.classes, 1, 1, 0, yf=self.logits, bias=self.fc_b)
-        K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, LOGIT_LD),
-                     None, self.grad_scale)
+        K.softmax_ce(self.logits, self.labels, self.loss, self.correct, self.dlogits.view(self.batch, self.logit_ld),
+                     None, self.grad_scale, **self._ce_kw)
 
     @contextlib.contextmanager
     def _ema_weights(self):
@@ -635,7 +645,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         """The held-out report (EvalReport) over EVERY record of (x, y), running statistics as in
         :meth:`evaluate`.  The set is padded with zero records to whole batches; per batch one
         ``forward_eval``, one ``sl_eval_accum`` launch that counts the batch's first ``n_valid`` rows into
-        a 264-word integer block on the device, and the cursor bump.  The host waits once, for the block
+        an integer block on the device (264 words up to 16 classes, 8 + classes^2 above), and the cursor bump.  The host waits once, for the block
         after the last batch: nothing in the loop reads the device.  Eval-mode BatchNorm normalises each
         row with the running statistics, so the padding rows cannot reach the valid ones.  ``ema=True``
         as in :meth:`evaluate`; training state, cursor and running statistics are bit-identical
@@ -647,10 +657,13 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                 return self.evaluate_full(x_u8, y_u8, topk=topk)
         x, y, N = self._eval_padded(x_u8, y_u8)
         B = self.batch
-        acc = E.new_acc(self.device)
+        ncls = self.spec.classes
+        # more than 16 classes: eval_accum_wide_kernel and its 8 + ncls^2 word block
+        accum, from_acc = (E.eval_accum_wide, E.report_from_acc_wide) if self.wide else (E.eval_accum, E.report_from_acc)
+        acc = E.new_acc_wide(self.device, ncls) if self.wide else E.new_acc(self.device)
         with self._eval_shard(x, y):
             for b in range(x.shape[0] // B):
                 self.forward_eval()
-                E.eval_accum(self.logits, self.labels, self.loss, min(B, N - b * B), self.spec.classes, topk, acc)
+                accum(self.logits, self.labels, self.loss, min(B, N - b * B), ncls, topk, acc)
                 self.K.cursor_bump(self.cursor)
-        return E.report_from_acc(acc, self.spec.classes, topk)
+        return from_acc(acc, ncls, topk)

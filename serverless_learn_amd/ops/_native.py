@@ -55,6 +55,7 @@ _SIGS: dict[str, list] = {
     "sl_comm_proxy": [P, P, L, I, P],
     # held-out evaluation metrics (eval_metrics.hip; ops/evalmetrics.py eval_accum)
     "sl_eval_accum": [P, I, P, P, I, I, I, I, P, P],
+    "sl_eval_accum_wide": [P, I, P, P, I, I, I, I, P, P],
 }
 _RESTYPE = {"sl_mlp_param_count": ctypes.c_long, "sl_mlp_slab_stride": ctypes.c_long,
             "sl_mlp_x_tile_bytes": ctypes.c_long}

@@ -46,6 +46,8 @@ N.register("sl_avgpool_fwd", [P, P, I, I, I, P])
 N.register("sl_avgpool_bwd", [P, P, I, I, I, P])
 N.register("sl_softmax_ce", [P, P, P, P, P, I, P, I, I, F, P])
 N.register("sl_softmax_ce_soft", [P, P, P, P, P, I, P, I, I, F, P, F, P])
+N.register("sl_softmax_ce_wide", [P, P, P, P, P, I, P, I, I, F, P, F, I, P, L, P])
+N.register("sl_softmax_ce_wide_ws_floats", [I, I], ctypes.c_long)
 N.register("sl_wgrad_side_begin", [P])
 N.register("sl_wgrad_side_join", [P, I])
 N.register("sl_conv3x3_c64_applicable", [I, I, I, I, I, I, I, I, I])
@@ -494,24 +496,69 @@ def avgpool_bwd(dy, dx):
     N.call("sl_avgpool_bwd", _bf16(dy), _bf16(dx), n, h * w, c, N.stream_ptr())
 
 
-def softmax_ce(logits, labels, loss, correct, dlogits, dbias, grad_scale):
+NARROW_CLASSES = 16  # softmax_ce_kernel: one row on a 16-lane group
+WIDE_CLASSES = 256   # softmax_ce_wide_kernel: one row on a wave, four classes per lane
+
+
+def logit_ld(ncls: int) -> int:
+    """Row stride of dlogits for ``ncls`` classes: 16 up to 16 classes, else the next power of two
+    ``>= max(32, ncls)`` (the FC data gradient reads dlogits as an image of that many channels)."""
+    if isinstance(ncls, bool) or int(ncls) != ncls or not 1 <= ncls <= WIDE_CLASSES:
+        raise ValueError(f"classes must be an integer in 1..{WIDE_CLASSES}, got {ncls!r}")
+    return 16 if ncls <= NARROW_CLASSES else max(32, 1 << (int(ncls) - 1).bit_length())
+
+
+def softmax_ce_wide_ws(n: int, ncls: int, device) -> torch.Tensor | None:
+    """The bias-gradient workspace of the wide loss for ``n`` rows (None up to 16 classes, where the
+    narrow kernel needs none).  It holds nothing between calls."""
+    if ncls <= NARROW_CLASSES:
+        return None
+    words = int(N.lib().sl_softmax_ce_wide_ws_floats(int(n), logit_ld(ncls)))
+    return torch.empty(max(words, 1), dtype=torch.float32, device=device)
+
+
+def _softmax_ce_wide(logits, labels, loss, correct, dlogits, dbias, grad_scale, mix, eps, soft, ws):
     n, ncls = logits.shape
+    if ws is None:
+        raise ValueError(f"softmax_ce over {ncls} classes needs the bias-gradient workspace (softmax_ce_wide_ws)")
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.device == logits.device
+    assert labels.dtype == torch.uint8 and labels.numel() >= n
+    assert dlogits.numel() >= n * dlogits.shape[-1] and (loss is None or loss.numel() >= n)
+    assert correct is None or correct.numel() >= n
+    assert dbias is None or dbias.numel() >= ncls
+    N.call("sl_softmax_ce_wide", _f32(logits), p(labels), _f32(loss), _f32(correct), _bf16(dlogits),
+           dlogits.shape[-1], _f32(dbias), n, ncls, float(grad_scale), p(mix) if mix is not None else None,
+           float(eps), 1 if soft else 0, p(ws), int(ws.numel()), N.stream_ptr())
+
+
+def softmax_ce(logits, labels, loss, correct, dlogits, dbias, grad_scale, ws=None):
+    """Softmax cross-entropy of fp32 ``logits`` [n, ncls] against u8 ``labels``: per-row ``loss`` and
+    ``correct``, ``dlogits`` (bf16 [n, ldd], zero beyond ncls) scaled by ``grad_scale``, and their row
+    sum added into ``dbias``.  Up to 16 classes the narrow kernel; 17..256 the wide one, which needs
+    ``ws`` (:func:`softmax_ce_wide_ws`) and ``ldd = logit_ld(ncls)`` or another power of two in
+    ``max(32, ncls)..256``."""
+    n, ncls = logits.shape
+    if ncls > NARROW_CLASSES:
+        return _softmax_ce_wide(logits, labels, loss, correct, dlogits, dbias, grad_scale, None, 0.0, False, ws)
     N.call("sl_softmax_ce", _f32(logits), p(labels), _f32(loss), _f32(correct), _bf16(dlogits), dlogits.shape[-1],
            _f32(dbias), n, ncls, float(grad_scale), N.stream_ptr())
 
 
-def softmax_ce_soft(logits, labels, loss, correct, dlogits, dbias, grad_scale, mix=None, eps: float = 0.0):
+def softmax_ce_soft(logits, labels, loss, correct, dlogits, dbias, grad_scale, mix=None, eps: float = 0.0, ws=None):
     """:func:`softmax_ce` against soft targets (data/augment.py ``soft_targets``): row i's target is
     ``(1 - eps)(wa [c = la] + wb [c = lb]) + eps / ncls`` with ``la = labels[i]`` and, from row i of
     ``mix`` (int32 [n, 8], :func:`input_mix`'s ``mix_out``; None = label smoothing alone),
     ``lb = labels[mix[i, 0]]``, ``wb = mix[i, 1] / mix[i, 2]``, ``wa = 1 - wb``.  ``correct`` stays the
-    argmax against ``la``: under mixing it is a diagnostic, not an accuracy."""
+    argmax against ``la``: under mixing it is a diagnostic, not an accuracy.  ``ws`` as in
+    :func:`softmax_ce`."""
     n, ncls = logits.shape
     if not 0 <= eps < 1:
         raise ValueError(f"label smoothing must be in [0, 1), got {eps!r}")
     assert labels.dtype == torch.uint8 and labels.numel() >= n
     if mix is not None:
         assert mix.dtype == torch.int32 and mix.numel() == 8 * n and mix.is_contiguous()
+    if ncls > NARROW_CLASSES:
+        return _softmax_ce_wide(logits, labels, loss, correct, dlogits, dbias, grad_scale, mix, eps, True, ws)
     N.call("sl_softmax_ce_soft", _f32(logits), p(labels), _f32(loss), _f32(correct), _bf16(dlogits),
            dlogits.shape[-1], _f32(dbias), n, ncls, float(grad_scale), p(mix) if mix is not None else None,
            float(eps), N.stream_ptr())

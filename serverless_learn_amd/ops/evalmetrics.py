@@ -4,7 +4,9 @@
 run it and ``eval_accum_kernel`` (csrc/kernels/eval_metrics.hip, :func:`eval_accum`) is tested
 against it field by field, exactly.
 
-For row ``i`` with logits ``z`` over ``ncls <= 16`` classes, label ``l`` (a label ``>= ncls`` counts
+For row ``i`` with logits ``z`` over ``ncls`` classes (up to 16 in ``eval_accum_kernel`` and the names
+without a suffix; up to 256 in ``eval_accum_wide_kernel`` and the ``*_wide`` names, whose device block is
+``int64 [8 + ncls * ncls]``), label ``l`` (a label ``>= ncls`` counts
 as 0, as in ``softmax_ce_kernel``) and ``loss_i`` the fp32 per-row loss the forward pass wrote:
 
 * the row is **bad** when a logit or the loss is not finite or ``|loss_i| >= 2^16``; a bad row adds
@@ -31,6 +33,7 @@ LOSS_FIX = float(1 << 24)       # loss_fix is the loss in units of 2^-24
 LOSS_BAD = float(1 << 16)       # |loss| at or past this marks a bad row
 ACC_HEAD = 8                    # counters in front of the confusion matrix in the device block
 ACC_LEN = ACC_HEAD + MAX_CLASSES * MAX_CLASSES
+WIDE_CLASSES = 256              # eval_accum_wide_kernel: the u8 label's range; its block is [8 + ncls * ncls]
 
 
 def check_topk(topk, ncls: int) -> int:
@@ -109,10 +112,12 @@ def _np(a, dtype):
     return np.asarray(a).astype(dtype, copy=False)
 
 
-def eval_reference(logits, labels, loss_rows, ncls: int, topk: int) -> EvalReport:
-    """The report of rows ``logits[i, :ncls]`` / ``labels[i]`` / ``loss_rows[i]`` (module docstring)."""
-    if not 1 <= ncls <= MAX_CLASSES:
-        raise ValueError(f"ncls must be in 1..{MAX_CLASSES}, got {ncls}")
+def eval_reference(logits, labels, loss_rows, ncls: int, topk: int, wide: bool = False) -> EvalReport:
+    """The report of rows ``logits[i, :ncls]`` / ``labels[i]`` / ``loss_rows[i]`` (module docstring).
+    ``wide``: up to :data:`WIDE_CLASSES` classes (``eval_accum_wide_kernel``'s range)."""
+    top = WIDE_CLASSES if wide else MAX_CLASSES
+    if not 1 <= ncls <= top:
+        raise ValueError(f"ncls must be in 1..{top}, got {ncls}")
     topk = check_topk(topk, ncls)
     z = _np(logits, np.float64)
     z = z.reshape(-1, z.shape[-1])[:, :ncls] if z.size else z.reshape(0, ncls)
@@ -168,3 +173,48 @@ def eval_accum(logits: torch.Tensor, labels: torch.Tensor, loss_rows: torch.Tens
         raise ValueError("eval_accum: a buffer is shorter than the rows")
     N.call("sl_eval_accum", N.ptr(logits), int(logits.stride(0)), N.ptr(labels), N.ptr(loss_rows), rows, int(n_valid),
            int(ncls), int(topk), N.ptr(acc), N.stream_ptr())
+
+
+# ---- up to 256 classes: a block of 8 + ncls * ncls words, the confusion matrix at stride ncls ----
+def _check_wide(ncls) -> int:
+    if isinstance(ncls, bool) or int(ncls) != ncls or not 1 <= ncls <= WIDE_CLASSES:
+        raise ValueError(f"ncls must be an integer in 1..{WIDE_CLASSES}, got {ncls!r}")
+    return int(ncls)
+
+
+def acc_len_wide(ncls: int) -> int:
+    ncls = _check_wide(ncls)
+    return ACC_HEAD + ncls * ncls
+
+
+def new_acc_wide(device, ncls: int) -> torch.Tensor:
+    return torch.zeros(acc_len_wide(ncls), dtype=torch.int64, device=device)
+
+
+def report_from_acc_wide(acc, ncls: int, topk: int) -> EvalReport:
+    """The report held by a wide device block (``int64 [8 + ncls * ncls]``, :func:`eval_accum_wide`)."""
+    n = acc_len_wide(ncls)
+    a = _np(acc, np.int64).reshape(-1)
+    if a.shape[0] < n:
+        raise ValueError(f"a block of {a.shape[0]} words for {ncls} classes: {n} needed")
+    conf = a[ACC_HEAD:n].reshape(ncls, ncls).copy()
+    return EvalReport(int(a[0]), int(a[1]), int(a[2]), int(a[3]), int(topk), int(a[4]), conf)
+
+
+def eval_accum_wide(logits: torch.Tensor, labels: torch.Tensor, loss_rows: torch.Tensor, n_valid: int, ncls: int,
+                    topk: int, acc: torch.Tensor) -> None:
+    """:func:`eval_accum` over up to 256 classes: one launch of ``eval_accum_wide_kernel`` adds the rows
+    ``[0, n_valid)`` into ``acc`` (:func:`new_acc_wide`)."""
+    from . import _native as N
+
+    rows = int(logits.shape[0])
+    if (logits.dtype != torch.float32 or loss_rows.dtype != torch.float32 or labels.dtype != torch.uint8
+            or acc.dtype != torch.int64):
+        raise TypeError("eval_accum_wide: fp32 logits and loss rows, u8 labels, an int64 block")
+    if logits.dim() != 2 or logits.stride(1) != 1 or not labels.is_contiguous() or not loss_rows.is_contiguous():
+        raise ValueError("eval_accum_wide: row-major logits, contiguous labels and loss rows")
+    if (labels.numel() < rows or loss_rows.numel() < rows or acc.numel() < acc_len_wide(ncls)
+            or not acc.is_contiguous()):
+        raise ValueError("eval_accum_wide: a buffer is shorter than the rows, or the block than 8 + ncls^2 words")
+    N.call("sl_eval_accum_wide", N.ptr(logits), int(logits.stride(0)), N.ptr(labels), N.ptr(loss_rows), rows,
+           int(n_valid), int(ncls), int(topk), N.ptr(acc), N.stream_ptr())

@@ -170,6 +170,8 @@ class Worker:
             kw.update(accum_steps=c.accum_for(world))
         if c.ema_decay != 0:  # (a bad decay is refused by Config and by OptSpec)
             kw.update(ema_decay=c.ema_decay, ema_warmup=c.ema_warmup)
+        if c.n_classes != 10:  # (Config refuses anything but ten for the MLP)
+            kw.update(classes=c.n_classes)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if c.ema_decay != 0:
             self.log.info("ema", decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
@@ -248,6 +250,11 @@ class Worker:
                 return pb.ReceiveFileAck(ok=False).SerializeToString()
             if n <= 0 or d <= 0 or HEADER_SIZE + n * d + n > got:
                 self.log.warn("ingest_bad_header", file_num=file_num, n=n, d=d, got=int(got))
+                return pb.ReceiveFileAck(ok=False).SerializeToString()
+            if self.cfg.model != "simulate" and hdr["classes"] > self.cfg.n_classes:
+                # labels >= the trainer's class count would silently be counted as class 0
+                self.log.warn("ingest_class_mismatch", file_num=file_num, shard_classes=int(hdr["classes"]),
+                              trainer_classes=self.cfg.n_classes)
                 return pb.ReceiveFileAck(ok=False).SerializeToString()
         dt = time.perf_counter() - t0
         self.bytes_ingested += got

@@ -52,6 +52,7 @@ class Case:
     bias: bool = False         # also a forward with a per-channel bias
     smallm: tuple = ()
     target_wgs: tuple = (2, 100, 384)   # split-K targets: slices == 1, a slice tail, the default
+    ldd: int = 0               # > 0: the channel stride of dy in both gradients (the engine's dlogits stride)
 
     @property
     def group(self) -> str:
@@ -173,6 +174,18 @@ CASES = [
 ]
 CASES_BY_NAME = {c.name: c for c in CASES}
 assert len(CASES_BY_NAME) == len(CASES)
+
+# The ResNet engine's FC layer over more than 16 classes (kept apart from CASES, which other tables
+# index): 37 rows of 512 features, a bias, and both gradients reading dy at the engine's dlogits
+# stride (ops.cnn.logit_ld: 128 for 100 classes, 256 for 250).  The first shapes with a partial
+# column tile after a full one (100 = 64 + 36, 250 = 128 + 122) and with an FC data gradient wider
+# than 16 channels.
+FC_CASES = (
+    _c("H1-fc-37x512-100", (37, 1, 1, 512, 100, 1, 1, 0), fwd=("gemm_64x128",), dgrad=("gemm_t_64x128",),
+       wgrad=("wgrad_128",), bias=True, ldd=128),
+    _c("H2-fc-37x512-250", (37, 1, 1, 512, 250, 1, 1, 0), fwd=("gemm_64x128",), dgrad=("gemm_t_64x128",),
+       wgrad=("wgrad_128",), bias=True, ldd=256),
+)
 
 
 def gemm_twin(case: Case) -> Case:
@@ -427,9 +440,11 @@ def run_case(case: Case, device="cuda", smallm: bool = False, keep: bool = False
 
         # the gradient dy padded to the launchers' channel strides: a multiple of 8 for the weight
         # gradient; a power of two for the data gradient (fill_geom needs one for its source)
-        dyp = torch.zeros(n, oh, ow, ldy, dtype=torch.bfloat16, device=device)
+        ldw = case.ldd or ldy
+        dyp = torch.zeros(n, oh, ow, ldw, dtype=torch.bfloat16, device=device)
         dyp[..., :cout] = o["dy"]
-        ldd = _next_pow2(ldy)
+        ldd = case.ldd or _next_pow2(ldy)
+        assert ldd >= cout and ldd & (ldd - 1) == 0 and ldw % 8 == 0, (case.name, ldd, ldw)
 
         def padded(t, ld):  # [.., cout] -> [.., ld]
             if ld == t.shape[-1]:
