@@ -19,11 +19,15 @@
 //   K_wgrad (mlp_wgrad_kernel) grouped split-K GEMM dW = dH^T . A over the
 //           batch for dW1 (A = raw u8 X, taken as the exact fp16 1024 + u
 //           against a power-of-two-scaled fp16 dH1: one v_perm per two
-//           elements) and dW2 (A = H1, bf16): 256x128 tiles; both
+//           elements) and dW2 (A = H1, bf16): 256x128 tiles, 8 waves of
+//           64 x 64; both
 //           operands stream global -> LDS by LDS-DMA (global_load_lds_dwordx4,
 //           no VGPR staging) into a 3-slot ring of XOR-swizzled [64 batch
 //           rows][128] images (two stages in flight, counted vmcnt + raw
-//           s_barrier), read transposed with ds_read_b64_tr_b16/_b8.
+//           s_barrier), read transposed with ds_read_b64_tr_b16/_b8.  dW1's
+//           six full tiles run as 128 (dH1 columns) x 256 (X columns) tiles:
+//           32 KB stages in a 4-slot ring, three in flight (WG_WSLOT).  The
+//           slab keeps one layout (TL_TILE) whatever tile computed an element.
 //           Deterministic fp32 slabs; each workgroup also sums a band of the
 //           rows kernel's partial rows ([dW3 | db3 | db1 | db2]) over its slice.
 //   K_sgd   (mlp_sgd_kernel)   slab reduction (+ optional all-reduce
@@ -1093,9 +1097,11 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_kernel(MlpRowArgs a) {
 // band of those columns over its slice's stages into the slice's slab, so the
 // slab carries every gradient and mlp_sgd_kernel needs no special case.
 // ---------------------------------------------------------------------------
-// Tiled slab layout (1): per slice, the 9 weight-gradient tiles in the order the
-// accumulators sit in the waves' registers -- tile t, wave w, store instruction (i, j), lane l,
-// 4 floats -- so every epilogue store is 1 KB of contiguous memory, then the rows kernel's
+// Tiled slab layout (1): per slice, the 9 weight-gradient 256 x 128 tiles in the order the
+// accumulators of 2 x 4 waves of 128 m x 32 n sit in registers -- tile t, wave w, store
+// instruction (i, j), lane l, 4 floats -- so every epilogue store (one 16 x 16 fragment) is 1 KB
+// of contiguous memory, whichever wave of whichever tile shape holds it (the epilogue maps its
+// 64 x 64 waves' fragments into this order), then the rows kernel's
 // partial-row sums in their own layout [dW3 | db3 | pad | db1 | db2].  The row-major form wrote
 // 16 rows x 64 B per store instruction; that tail took ~16 us (knockout, profiles/r03_wgrad).
 constexpr long TL_TILE = 256L * 128;            // floats per 256 x 128 tile
@@ -1112,8 +1118,13 @@ struct WgProblem {
   int bias_part;      // this problem's db partial inside the rows kernel's partial rows
 };
 // weight-gradient stamps per logical workgroup: start / main loop done / end (s_memtime), XCC_ID,
-// start / end s_memrealtime (100 MHz)
+// start / end s_memrealtime (100 MHz).  A diagnostic build with -DSL_WG_WAITSTAMP adds the ticks wave 0
+// spent in the main loop's wg_vmcnt and s_barrier (scripts/wgrad_stage_stamps.py).
+#ifdef SL_WG_WAITSTAMP
+constexpr int WG_STAMPS = 8;
+#else
 constexpr int WG_STAMPS = 6;
+#endif
 
 struct WgArgs {
   WgProblem p[2];  // dW1 (u8 X), dW2 (H1); dW3 comes from the rows kernel's partials
@@ -1126,12 +1137,20 @@ struct WgArgs {
   const float* w3p;      // [n_w3p][W3P_LD] partial rows of the rows kernel (one per rows workgroup)
   int n_w3p;
   unsigned long long* stamps;  // diagnostics: [logical workgroup][WG_STAMPS] (nullptr in production)
+  int wide;                    // dW1 tiles 0..5 run as 128 x 256 tiles on the 4-slot ring (0: the 256 x 128 loop)
 };
 
 constexpr int WG_NSLOT = 3;               // LDS ring slots (144 KB): two stages in flight
 constexpr int WG_IMG = 64 * 128;          // one [64 k][128] bf16 image, unpadded (swizzled)
 constexpr int WG_SLOT = 3 * WG_IMG;       // A half 0, A half 1, B = 48 KB
 constexpr int WG_LDS = WG_NSLOT * WG_SLOT;
+// Wide dW1 tiles: 128 dH1 columns x 256 X columns.  A stage is ONE fp16 image of dH1 (the left or
+// right half of its rows, 16 KB) and TWO u8 images of X (128 columns each, 8 + 8 KB): 32 KB
+// against the 40 KB of a 256 x 128 stage, so four slots fit (128 KB) and three stages are in
+// flight.  The images are the 256 x 128 loop's own, so its swizzles and tr-read addresses hold.
+constexpr int WG_WNSLOT = 4;
+constexpr int WG_WSLOT = 2 * WG_IMG;
+static_assert(WG_WNSLOT * WG_WSLOT <= WG_LDS, "the wide ring lives in the same LDS array");
 
 // 16-B chunk position inside a 256-B image row.  XOR on chunk-pair bits with
 // f(r) = (r & 3) | ((r >> 3) & 1) << 2 makes every ds_read_b64_tr_b16 of the
@@ -1228,6 +1247,11 @@ __device__ __forceinline__ void wg_vmcnt(int younger) {
 // remaining 31 dW2 tiles -- 2 of the 28 dW2 pairs straddle XCDs, no dW1 group does.  The
 // generic remap (consecutive logical tiles per XCD, 9 per slice) splits about 7 slices
 // (profiles/r06_place: 195 MB read for 164 MB of operands).  Other grids keep it.
+// The wide form of dW1 keeps the count and the numbering: tiles 0..5 of a slice are then the
+// 2 m-halves x 3 n-tiles of 128 x 256 (tile t: half t & 1, X columns 256 (t >> 1) ..), tile 6 is
+// still the 16-column tail over all 256 m, served by one workgroup with the 256 x 128 loop -- 9
+// tiles x 28 slices = 252 workgroups as before, a slice's dW1 tiles on one XCD, each dH1 half
+// read by three of them and each X brick by two.
 __device__ __forceinline__ void wg_place(int bid, int nwg, int total_tiles, int& s, int& t) {
   if (nwg == 252 && total_tiles == 9) {
     const int x = bid & 7, idx = bid >> 3;
@@ -1247,8 +1271,14 @@ __device__ __forceinline__ void wg_place(int bid, int nwg, int total_tiles, int&
 }
 
 constexpr int WG_NT = 512;
-constexpr int WG_MI = 8;  // 16-row A (dZ) fragments per wave
-constexpr int WG_NJ = 2;  // 16-column B fragments per wave
+// A wave's 64 accumulators per lane as 64 m x 64 n: per 64-row stage it reads 4 + 4 fragments per
+// k-step from LDS, 12 KB with u8 B fragments (16 KB with bf16 ones), where 128 m x 32 n read
+// 8 + 2, 18 KB (20 KB).  The main loop is bound by LDS bandwidth -- 8 waves x 18 KB of reads plus
+// the stage's 40 KB of LDS-DMA writes are ~1,450 cycles at 128 B per cycle against 1,024 MFMA
+// cycles (profiles/r19_wgring) -- and the u8 conversions the wider B side doubles are 4 v_perm
+// per fragment.
+constexpr int WG_MI = 4;  // 16-row A (dZ) fragments per wave
+constexpr int WG_NJ = 4;  // 16-column B fragments per wave
 constexpr int WG_NF = WG_MI + WG_NJ;       // fragments per wave per k-step
 
 // XT: problem 0's B operand is the tiled shard (a stage is one 64-row block, tile tn covers
@@ -1259,7 +1289,6 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[WG_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: branches on it stay uniform
-  const int wm = wave & 1, wn = wave >> 1;
   const int lr = lane & 15, lg = lane >> 4;
   int s, t;
   wg_place(blockIdx.x, gridDim.x, A.total_tiles, s, t);
@@ -1267,7 +1296,13 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   const int pi = t >= A.p[1].tile_base ? 1 : 0;
   const WgProblem& P = A.p[pi];
   const int tn = t - P.tile_base;
-  const int n0 = tn * 128;
+  // Wide form of dW1's six full tiles: tile tn is m-half tn & 1 (128 dH1 columns) of X columns
+  // 256 (tn >> 1) .. +255.  Every wave holds 64 m x 64 n: 4 x 2 waves over a 256 x 128 tile,
+  // 2 x 4 over a wide one.
+  const bool wide = A.wide != 0 && pi == 0 && tn < 6;
+  const int wm = wide ? wave & 1 : wave & 3, wn = wide ? wave >> 1 : wave >> 2;
+  const int tn8 = wide ? (tn >> 1) * 2 : tn;  // the 128-column X tile of (the first) B image
+  const int n0 = tn8 * 128;
   const int st0 = s * A.steps_per_slice;
   const int nst = min(A.steps_per_slice, A.total_steps - st0);
   const bool u8b = pi == 0;
@@ -1291,35 +1326,50 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   for (int j = 0; j < 2; ++j) {
     const int row = 4 * (2 * wave + j) + prow;
     const int c = wg_swz(lane & 15, row);
-    asrc[j] = static_cast<const uint16_t*>(P.a) + (long)(st0 * 64 + row) * HID + c * 8;
+    // wide: the one A image is the tile's half of the dH1 row
+    asrc[j] = static_cast<const uint16_t*>(P.a) + (long)(st0 * 64 + row) * HID + c * 8 + (wide ? (tn & 1) * 128 : 0);
     bsrc[j] = static_cast<const uint16_t*>(P.b) + (long)(st0 * 64 + row) * P.ldb + n0 + c * 8;
   }
+  // wide: the second u8 image is the next 128 columns (two bricks on / 128 B along the row)
+  // (a workgroup-uniform base and a 32-bit lane offset: the per-stage and per-image steps stay scalar)
   const uint8_t* bsrc8;
+  uint32_t boff8;
   {
     const int row = 8 * wave + (lane >> 3);
     const int c = wg_swz8(lane & 7, row);
     if constexpr (XT) {
-      const int brick = min(2 * tn + (c >> 2), NCHUNK - 1);  // past the last brick: don't-care columns of dW1
-      bsrc8 = static_cast<const uint8_t*>(P.b) + ((xrow0 >> 6) + st0) * XT_RB + brick * XT_BRICK + row * 64 + (c & 3) * 16;
+      const int brick = min(2 * tn8 + (c >> 2), NCHUNK - 1);  // past the last brick: don't-care columns of dW1
+      bsrc8 = static_cast<const uint8_t*>(P.b) + ((xrow0 >> 6) + st0) * XT_RB;
+      boff8 = (uint32_t)(brick * XT_BRICK + row * 64 + (c & 3) * 16);
     } else {
       const int col = min(n0 + c * 16, P.ldb - 16);  // columns >= 784 are don't-care columns of dW1
-      bsrc8 = static_cast<const uint8_t*>(P.b) + (xrow0 + st0 * 64 + row) * P.ldb + col;
+      bsrc8 = static_cast<const uint8_t*>(P.b) + (xrow0 + st0 * 64) * P.ldb;
+      boff8 = (uint32_t)(row * P.ldb + col);
     }
   }
   const long bstep8 = XT ? XT_RB : 64 * P.ldb;  // u8 B: bytes per stage
-  auto issue = [&](int st, auto u8_c) {  // stage st (relative to the slice) -> ring slot st % NS
-    constexpr bool U8 = decltype(u8_c)::value;
-    uint16_t* Ai = smem + (st % WG_NSLOT) * WG_SLOT;
-    uint16_t* Bi = Ai + 2 * WG_IMG;
+  const long bimg8 = XT ? 2 * XT_BRICK : 128;  // wide: from the first u8 image's source to the second's
+  // loop form M: 0 = dW2 (bf16 B), 1 = dW1 256 x 128 (u8 B), 2 = dW1 wide (one A image, two u8 B images)
+  auto issue = [&](int st, auto m_c) {  // stage st (relative to the slice) -> ring slot st % NS
+    constexpr int M = decltype(m_c)::value;
+    constexpr int NA = M == 2 ? 1 : 2;
+    uint16_t* Ai = smem + (M == 2 ? (st % WG_WNSLOT) * WG_WSLOT : (st % WG_NSLOT) * WG_SLOT);
+    uint16_t* Bi = Ai + NA * WG_IMG;
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < NA; ++h)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) void*)(asrc[j] + (long)st * 64 * HID + h * 128),
             (SL_LDS void*)(Ai + h * WG_IMG + 4 * (2 * wave + j) * 128), 16, 0, 0);
-    if constexpr (U8) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc8 + (long)st * bstep8),
+    if constexpr (M == 2) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(bsrc8 + (long)st * bstep8 + h * bimg8 + boff8),
+            (SL_LDS void*)(reinterpret_cast<uint8_t*>(Bi) + h * 64 * 128 + 8 * wave * 128), 16, 0, 0);
+    } else if constexpr (M == 1) {
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc8 + (long)st * bstep8 + boff8),
                                        (SL_LDS void*)(reinterpret_cast<uint8_t*>(Bi) + 8 * wave * 128), 16, 0, 0);
     } else {
 #pragma unroll
@@ -1328,12 +1378,15 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
                                          (SL_LDS void*)(Bi + 4 * (2 * wave + j) * 128), 16, 0, 0);
     }
   };
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  if (u8b) {
-    for (int st = 0; st < WG_NSLOT - 1 && st < nst; ++st) issue(st, T_{});
+  using M0 = std::integral_constant<int, 0>;
+  using M1 = std::integral_constant<int, 1>;
+  using M2 = std::integral_constant<int, 2>;
+  if (wide) {
+    for (int st = 0; st < WG_WNSLOT - 1 && st < nst; ++st) issue(st, M2{});
+  } else if (u8b) {
+    for (int st = 0; st < WG_NSLOT - 1 && st < nst; ++st) issue(st, M1{});
   } else {
-    for (int st = 0; st < WG_NSLOT - 1 && st < nst; ++st) issue(st, F_{});
+    for (int st = 0; st < WG_NSLOT - 1 && st < nst; ++st) issue(st, M0{});
   }
 
   floatx4_t acc[WG_MI][WG_NJ];
@@ -1353,7 +1406,8 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
 #pragma unroll
   for (int j = 0; j < WG_NJ; ++j) {
     const int c = wn * 16 * WG_NJ + j * 16;
-    b_addr[j] = 2 * WG_IMG * 2 + (u8b ? wg_tr8_addr(c, lane) : wg_tr_addr(c, lane));
+    if (wide) b_addr[j] = WG_IMG * 2 + (c >> 7) * 64 * 128 + wg_tr8_addr(c & 127, lane);  // u8 image c / 128
+    else b_addr[j] = 2 * WG_IMG * 2 + (u8b ? wg_tr8_addr(c, lane) : wg_tr_addr(c, lane));
   }
 
   // Instantiated per (u8, live n-blocks) and selected by a scalar branch OUTSIDE the loop
@@ -1365,13 +1419,18 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   // per stage back to back (knockout "reads + MFMAs only": 45.7 us).
   // The slot of stage st is refilled (stage st+3) after the barrier of step st,
   // when every wave has waited for its own reads of stage st.
+#ifdef SL_WG_WAITSTAMP
+  unsigned long long wait_vm = 0, wait_bar = 0;  // wave 0's s_memtime ticks in the steps' wg_vmcnt / s_barrier
+#endif
   auto mainloop_pipe = [&](auto u8_c, auto nb_c) {
-    constexpr bool U8 = decltype(u8_c)::value;
+    constexpr int M = decltype(u8_c)::value;  // loop form, as in the issue lambda above
+    constexpr bool U8 = M != 0;
     constexpr int NB = decltype(nb_c)::value;
     constexpr int NBR = NB > 0 ? NB : 1;
-    constexpr int PPS = U8 ? 5 : 6;
+    constexpr int PPS = M == 2 ? 4 : U8 ? 5 : 6;  // LDS-DMA pieces per wave per stage
     constexpr int KB = U8 ? 4096 : 8192;
-    constexpr int NS = WG_NSLOT, SLOT = WG_SLOT;  // ring depth / slot stride (uint16)
+    constexpr int NS = M == 2 ? WG_WNSLOT : WG_NSLOT;  // ring depth: NS - 1 stages in flight
+    constexpr int SLOT = M == 2 ? WG_WSLOT : WG_SLOT;  // slot stride (uint16)
     short8_t fa[2][2][WG_MI]; // [set][k-step][m-block]
     short8_t fb[2][2][NBR];   // bf16 B fragments
     uint2v_t fr[2][2][NBR];   // raw u8 B fragments (converted next to their MFMAs)
@@ -1430,8 +1489,18 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
     auto step = [&](int st, auto cur_c, auto nxt_c) {
       constexpr int C = decltype(cur_c)::value;
       if (st + 1 < nst) {
+#ifdef SL_WG_WAITSTAMP
+        const unsigned long long w0 = __builtin_amdgcn_s_memtime();
+#endif
         wg_vmcnt<PPS>(min(NS - 2, nst - 2 - st));  // stage st+1 has landed (st+2 .. st+NS-1 may be in flight)
+#ifdef SL_WG_WAITSTAMP
+        const unsigned long long w1 = __builtin_amdgcn_s_memtime();
+#endif
         __builtin_amdgcn_s_barrier();          // ... for everyone; every wave is done reading stage st
+#ifdef SL_WG_WAITSTAMP
+        wait_vm += w1 - w0;
+        wait_bar += __builtin_amdgcn_s_memtime() - w1;
+#endif
         if (st + NS < nst) issue(st + NS, u8_c);  // into stage st's slot
       }
       const uint32_t sbn = lds_base + (uint32_t)((min(st + 1, nst - 1) % NS) * SLOT * 2);
@@ -1508,15 +1577,23 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   using I4 = std::integral_constant<int, WG_NJ>;  // all n-blocks live
   using I1 = std::integral_constant<int, 1>;
   using I0 = std::integral_constant<int, 0>;
-  if (u8b) {
-    if (nvalid >= WG_NJ) mainloop_pipe(T_{}, I4{});
-    else if (nvalid >= 1) mainloop_pipe(T_{}, I1{});
-    else mainloop_pipe(T_{}, I0{});
+  if (wide) {
+    mainloop_pipe(M2{}, I4{});
+  } else if (u8b) {
+    if (nvalid >= WG_NJ) mainloop_pipe(M1{}, I4{});
+    else if (nvalid >= 1) mainloop_pipe(M1{}, I1{});
+    else mainloop_pipe(M1{}, I0{});
   } else {
-    mainloop_pipe(F_{}, I4{});
+    mainloop_pipe(M0{}, I4{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (A.stamps && tid == 0) A.stamps[logical * WG_STAMPS + 1] = __builtin_amdgcn_s_memtime();
+  if (A.stamps && tid == 0) {
+    A.stamps[logical * WG_STAMPS + 1] = __builtin_amdgcn_s_memtime();
+#ifdef SL_WG_WAITSTAMP
+    A.stamps[logical * WG_STAMPS + 6] = wait_vm;
+    A.stamps[logical * WG_STAMPS + 7] = wait_bar;
+#endif
+  }
 
   // ---- the slice's sums of the rows kernel's partial rows ([dW3 | db3 | db1 | db2], one per
   // rows workgroup): slice s sums partial rows [s ppr, (s + 1) ppr) -- any partition of them
@@ -1546,11 +1623,18 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
   // ---- epilogue: the MFMAs took their operands swapped (B first), so each lane holds
   // 4 consecutive n of one m row: float4 stores straight from registers into slab slice
   // s (no LDS staging, no barriers) ----
-  static_assert(WG_MI == 8 && WG_NJ == 2, "tiled slab assumes 2 x 4 waves of 128 x 32");
-  float* out = A.slab + (long)s * A.slab_stride + (pi ? TL_W2 : 0) + (long)tn * TL_TILE + wave * 4096 + lane * 4;
-  // buffer stores of this wave's 16 KB of the tile (a wave-uniform base): lane offset + constant per store
-  float* out_base = A.slab + (long)s * A.slab_stride + (pi ? TL_W2 : 0) + (long)tn * TL_TILE + wave * 4096;
-  const auto out_rs = __builtin_amdgcn_make_buffer_rsrc(out_base, 0, WG_MI * WG_NJ * 1024, 0x00020000);
+  static_assert(WG_MI == 4 && WG_NJ == 4, "the slab map below is that of 64 x 64 waves");
+  // The slab keeps the order of 2 x 4 waves of 128 m x 32 n over 256 x 128 tiles (TL_TILE): the
+  // fragment of m-block mi (16 rows, 0..15) and n-block nl (16 columns, 0..7) of such a tile is
+  // the 1 KB at wave (mi >> 3) + 2 (nl >> 1), store (mi & 7) * 2 + (nl & 1).  This wave's blocks
+  // start at mb and nb, both multiples of 4 (nb counts from column n0 and runs into the next
+  // 256 x 128 tile in the wide form): fragment (i, j) lies a constant behind the wave's first.
+  const int mb = (wide ? (tn & 1) * 8 : 0) + wm * 4, nb = wn * 4;
+  const int tile_o = tn8 + (nb >> 3), wave_o = (mb >> 3) + 2 * ((nb & 7) >> 1);
+  float* out_base = A.slab + (long)s * A.slab_stride + (pi ? TL_W2 : 0) + (long)tile_o * TL_TILE + wave_o * 4096 +
+                    (mb & 7) * 2 * 256;
+  // buffer stores (a wave-uniform base): lane offset + constant per store
+  const auto out_rs = __builtin_amdgcn_make_buffer_rsrc(out_base, 0, (2 * 4096 + WG_MI * 2 * 256) * 4, 0x00020000);
   const int out_voff = lane * 16;
 #pragma unroll
   for (int i = 0; i < WG_MI; ++i)
@@ -1560,7 +1644,7 @@ __global__ __launch_bounds__(WG_NT, 1) void mlp_wgrad_kernel(WgArgs A) {
       if (n < P.n_real) {
         typedef uint32_t u32x4w __attribute__((ext_vector_type(4)));
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, acc[i][j]), out_rs, out_voff,
-                                               (i * WG_NJ + j) * 1024, 0);
+                                               ((j >> 1) * 2 * 4096 + (i * 2 + (j & 1)) * 256) * 4, 0);
       }
     }
 
@@ -2099,6 +2183,12 @@ int sl_mlp_set_wg_stamps(unsigned long long* p) {  // weight-gradient stamps (di
   g_wg_stamps = p;
   return 0;
 }
+int sl_mlp_wg_stamps() { return WG_STAMPS; }  // stamps per workgroup in this build
+static int g_wg_wide = 1;  // 0: dW1's full tiles run the 256 x 128 loop too (tests, A/B; the slab is the same)
+int sl_mlp_set_wg_wide(int on) {
+  g_wg_wide = on != 0;
+  return 0;
+}
 static int g_rows_bm = 0;  // 0: auto; 64 / 128 force a tile height (benchmarks, tests)
 int sl_mlp_set_rows_bm(int bm) {
   g_rows_bm = bm;
@@ -2207,6 +2297,8 @@ static int mlp_wgrad_launch(bool xt, int batch, const uint8_t* x, const int* cur
   a.cursor = cursor; a.n_batches = n_batches > 0 ? n_batches : 1; a.batch = batch;
   a.w3p = w3p; a.n_w3p = n_w3p;
   a.stamps = g_wg_stamps;
+  a.wide = g_wg_wide;
+  static_assert((D_IN + 127) / 128 == 7 && D_IN >= 6 * 128, "wide dW1 tiles: six full 128-column tiles and a tail");
   if (((uintptr_t)x & 15) != 0 || ((uintptr_t)w3p & 15) != 0) return -2;  // 16-B pieces / float4 reads
   if (xt) hipLaunchKernelGGL(mlp_wgrad_kernel<true>, dim3(base * slices), dim3(WG_NT), 0, stream, a);
   else hipLaunchKernelGGL(mlp_wgrad_kernel<false>, dim3(base * slices), dim3(WG_NT), 0, stream, a);
