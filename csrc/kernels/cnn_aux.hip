@@ -1004,9 +1004,6 @@ static long ce_wide_parts(int N) {
 }
 
 // ---------------------------------------------------------------------------
-extern "C" int sl_rsum_fold(float* buf, int n, hipStream_t stream);  // conv.hip
-extern "C" int sl_rsum_fold2(float* buf, float* buf2, int n, hipStream_t stream);  // conv.hip
-
 static NormCoef norm_coef(float m0, float m1, float m2, float s0, float s1, float s2) {
   return NormCoef{1.f / (255.f * s0), 1.f / (255.f * s1), 1.f / (255.f * s2), -m0 / s0, -m1 / s1, -m2 / s2};
 }

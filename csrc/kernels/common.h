@@ -192,7 +192,8 @@ enum SlConvFamily {
   SL_KF_HALO_FWD_C64, SL_KF_HALO_FWD_C8, SL_KF_HALO_DGRAD, SL_KF_HALO_WGRAD,   // conv3x3_halo.hip
   SL_KF_COUNT
 };
-extern "C" void sl_conv_note_kernel(int family);
+
+#include "sl_api.h"  // every exported sl_* entry point, declared once
 
 #define SL_CHECK_LAUNCH() \
   do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return (int)_e; } while (0)

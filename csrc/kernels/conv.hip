@@ -1955,15 +1955,6 @@ int sl_conv_set_phase(int on) {
   g_conv_phase = on;
   return 0;
 }
-// conv3x3_halo.hip: direct kernel for 3x3/s1/p1 64->64 convolutions on 32-wide images
-int sl_conv3x3_c64_applicable(int H, int W, int C, int cout, int KH, int KW, int stride, int pad, int ldw);
-int sl_conv3x3_c64(const uint16_t* src, const uint16_t* w, int cin, int flip, int N, int H, uint16_t* y, int ldy,
-                   const uint16_t* add, float* stats, hipStream_t stream);
-int sl_conv3x3_c64_bn(const uint16_t* src, const uint16_t* w, int cin, int flip, int N, int H, uint16_t* y, int ldy,
-                      const uint16_t* add, float* stats, const BnBwdEpi* bn, hipStream_t stream);
-int sl_conv3x3_wgrad_c64_applicable(int H, int W, int C, int cout, int KH, int KW, int stride, int pad, int ldy);
-int sl_conv3x3_wgrad_c64(const uint16_t* x, const uint16_t* dy, int ldy, int N, int H, float* dw, float* ws,
-                         long ws_floats, hipStream_t stream);
 
 // Forward: x [N][H][W][C] -> y [N][OH][OW][ldy] (cols < cout), w [cout][KH][KW][C].
 int sl_conv_fwd(const uint16_t* x, int N, int H, int W, int C, const uint16_t* w, int cout, int KH, int KW,

@@ -499,8 +499,6 @@ int sl_conv3x3_c64(const uint16_t* src, const uint16_t* w, int cin, int flip, in
   return sl_conv3x3_c64_bn(src, w, cin, flip, N, H, y, ldy, add, stats, nullptr, stream);
 }
 
-int sl_rsum_fold(float* buf, int n, hipStream_t stream);
-
 // Forward 64 -> 64 conv of relu(bn(x)) straight from the BN input x: the BN's folded sums
 // (bstats), gamma / beta give the per-channel scale / shift, applied to each halo chunk
 // between its load and the LDS store; workgroup 0 writes the BN's coef / running stats.
@@ -820,12 +818,6 @@ extern "C" {
 int sl_conv3x3_wgrad_c64_applicable(int H, int W, int C, int cout, int KH, int KW, int stride, int pad, int ldy) {
   return sl_conv3x3_c64_applicable(H, W, C, cout, KH, KW, stride, pad, C) && C == HC && ldy == HC;
 }
-
-int sl_wgrad_slab_reduce(const float* ws, int slices, long n, float* dw, hipStream_t stream);
-void sl_wgrad_slab_acquire(const float* ws, hipStream_t main);   // conv.hip: side-stream reduces
-hipStream_t sl_wgrad_reduce_stream(hipStream_t main);
-void sl_wgrad_reduce_done(const float* ws, hipStream_t rs);
-void sl_wgrad_note_need(long floats);
 
 static int conv3x3_wgrad_launch(const uint16_t* x, const uint16_t* dy, int ldy, int N, int H, float* dw, float* ws,
                                 long ws_floats, const BnStats* bin, float bin_count, float bin_eps,

@@ -21,6 +21,7 @@ from __future__ import annotations
 import argparse
 import glob
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -30,6 +31,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE_DIR = os.path.join(ROOT, "serverless_learn_amd", "_native")
 KERNEL_DIR = os.path.join(ROOT, "csrc", "kernels")
 CORE_DIR = os.path.join(ROOT, "csrc", "core")
+# the one declaration of every exported sl_* kernel entry point: the compiler checks the
+# definitions against it, ops/_native.py derives the ctypes signatures from it
+API_HEADER = os.path.join(KERNEL_DIR, "sl_api.h")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("SL_OFFLOAD_ARCH", "gfx950")
 
@@ -100,8 +104,40 @@ def build_kernels(force: bool = False, jobs: int = 8, deterministic: bool = Fals
     tmp = so_path + ".tmp"
     _run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", *objs, "-o", tmp])
     _check_stubs(tmp)
+    _check_exports(tmp)
     os.replace(tmp, so_path)
     return so_path
+
+
+def _nm() -> str:
+    return shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+
+
+def api_names() -> set[str]:
+    """The entry points that csrc/kernels/sl_api.h declares (ops/_native.py parses their types)."""
+    with open(API_HEADER) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    return set(re.findall(r"\b(sl_\w+)\s*\(", text))
+
+
+def exported_names(so: str) -> set[str]:
+    """The defined dynamic ``sl_*`` symbols of a kernel library."""
+    proc = subprocess.run([_nm(), "-D", "--defined-only", so], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                          text=True, check=True)
+    return {ln.split()[-1] for ln in proc.stdout.splitlines() if ln.split() and ln.split()[-1].startswith("sl_")}
+
+
+def _check_exports(so: str, exported: set[str] | None = None) -> None:
+    """Refuse a kernel library whose exported ``sl_*`` symbols are not exactly the names that
+    sl_api.h declares.  The compiler holds every definition to its declaration but cannot see an
+    export that has none; Python would call that one with guessed argument types."""
+    if exported is None:
+        exported = exported_names(so)
+    declared = api_names()
+    extra, missing = sorted(exported - declared), sorted(declared - exported)
+    if extra or missing:
+        raise RuntimeError("%s and sl_api.h disagree: exported but not declared: %s; declared but not exported: %s"
+                           % (so, ", ".join(extra) or "none", ", ".join(missing) or "none"))
 
 
 def _check_stubs(so: str) -> None:
@@ -109,8 +145,7 @@ def _check_stubs(so: str) -> None:
     names a device-only builtin in a type-dependent expression fails host-side instantiation
     silently: its launch stub is left undefined and the library only fails at dlopen, on the
     GPU box (csrc/kernels/conv.hip `blds16` is the wrapper that avoids this)."""
-    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    proc = subprocess.run([nm, "-D", "--undefined-only", so], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+    proc = subprocess.run([_nm(), "-D", "--undefined-only", so], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                           text=True)
     missing = [ln.split()[-1] for ln in proc.stdout.splitlines() if "__device_stub__" in ln]
     if missing:

@@ -5,6 +5,12 @@ success (non-zero = hipError_t or an argument error).  Launchers are cheap to
 call and are captured into hipGraphs by ``torch.cuda.graph`` because they
 launch on the caller's current stream.
 
+The signatures are not written here.  ``csrc/kernels/sl_api.h`` declares every
+exported ``sl_*`` function once; the compiler holds each definition to it, and
+:func:`parse_api` reads the same text at import to derive ``_SIGS`` (name ->
+argtypes) and ``_RESTYPE`` (name -> restype), so every export has its argtypes
+and a Python signature cannot drift from the C one.
+
 There is deliberately NO silent fallback: on a machine with a GPU the ops
 raise if the extension is missing or fails, so a test can never pass on an
 eager PyTorch path while claiming to exercise the HIP kernels.
@@ -13,69 +19,75 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 
 import torch
 
-from ..build import KERNELS_DET_SO, KERNELS_SO
+from ..build import API_HEADER, KERNELS_DET_SO, KERNELS_SO
 
 _lock = threading.Lock()
 _lib = None
 _lib_is_default = True  # False: an A/B build loaded through SL_KERNELS_SO, which may lack newer kernels
 
-P = ctypes.c_void_p
-I = ctypes.c_int
-L = ctypes.c_long
-F = ctypes.c_float
-
-# name -> argtypes (restype is always c_int unless listed in _RESTYPE)
-_SIGS: dict[str, list] = {
-    "sl_mlp_param_count": [],
-    "sl_mlp_slab_stride": [],
-    "sl_mlp_rows": [P, P, P, I, I, P, P, P, P, P, P, F, F, F, F, P, P, P, P, P, P, P, I, P, P, P],
-    "sl_mlp_wgrad": [I, P, P, I, P, P, P, P, I, P, I, L, P],
-    # the same two launches reading X from the tiled shard (sl_mlp_x_tile)
-    "sl_mlp_rows_xt": [P, P, P, I, I, P, P, P, P, P, P, F, F, F, F, P, P, P, P, P, P, P, I, P, P, P],
-    "sl_mlp_wgrad_xt": [I, P, P, I, P, P, P, P, I, P, I, L, P],
-    "sl_mlp_x_tile": [P, P, L, P],
-    "sl_mlp_x_tile_bytes": [L],
-    "sl_mlp_wgrad_slices": [I, I],
-    "sl_mlp_set_rows_bm": [I],
-    "sl_conv_set_halo": [I],
-    "sl_conv_set_phase": [I],
-    "sl_mlp_rows_bm": [I],
-    "sl_mlp_set_stamps": [P],
-    "sl_mlp_set_wg_stamps": [P],
-    "sl_mlp_wg_stamps": [],
-    "sl_mlp_set_wg_wide": [I],
-    "sl_mlp_set_sgd_stamps": [P],
-    "sl_mlp_sgd_wgs": [],
-    "sl_mlp_sgd": [P, P, P, I, L, P, P, F, F, F, F, F, I, P, P, P, P, P, P, P, P],
-    "sl_mlp_reduce_xgmi": [P, I, L, F, F, P, P, P, P, L, I, I, L, I, P],
-    "sl_mlp_sgd_xgmi": [P, P, F, F, F, P, P, P, P, P, P, P, P, L, I, I, L, P, I, P],
-    "sl_clock_probe": [P, P, I, P],
-    "sl_comm_proxy": [P, P, L, I, P],
-    # held-out evaluation metrics (eval_metrics.hip; ops/evalmetrics.py eval_accum)
-    "sl_eval_accum": [P, I, P, P, I, I, I, I, P, P],
-    "sl_eval_accum_wide": [P, I, P, P, I, I, I, I, P, P],
+# the header's whole type vocabulary (plus: anything with a '*' is a pointer)
+_CTYPES = {
+    "int": ctypes.c_int, "unsigned": ctypes.c_uint, "long": ctypes.c_long, "long long": ctypes.c_longlong,
+    "unsigned long long": ctypes.c_ulonglong, "float": ctypes.c_float, "double": ctypes.c_double,
+    "hipStream_t": ctypes.c_void_p,
 }
-_RESTYPE = {"sl_mlp_param_count": ctypes.c_long, "sl_mlp_slab_stride": ctypes.c_long,
-            "sl_mlp_x_tile_bytes": ctypes.c_long}
+_TYPE_WORDS = {"int", "unsigned", "long", "float", "double", "void", "hipStream_t"}
+_DECL = re.compile(r"([\w\s:*]+?)\b(\w+)\s*\(([^()]*)\)")
 
 
-def register(name: str, argtypes: list, restype=ctypes.c_int) -> None:
-    """Register a launcher signature (used by the op modules at import)."""
-    _SIGS[name] = argtypes
-    if restype is not ctypes.c_int:
-        _RESTYPE[name] = restype
-    if _lib is not None and (_lib_is_default or hasattr(_lib, name)):  # (an A/B build: as in lib())
-        _bind(_lib, name)
+def _ctype(text: str, decl: str, named: bool):
+    """ctypes type of one parameter (``named``: a trailing parameter name is dropped) or return type."""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return ctypes.c_void_p
+    if named and len(words) > 1 and words[-1] not in _TYPE_WORDS:
+        words.pop()
+    try:
+        return _CTYPES[" ".join(words)]
+    except KeyError:
+        raise ValueError(f"sl_api.h: type {text.strip()!r} is outside the ABI's vocabulary in: {decl}") from None
+
+
+def parse_api(text: str) -> dict[str, tuple]:
+    """``{name: (restype, argtypes)}`` for every ``RET NAME(PARAMS);`` in the extern "C" block of
+    a header's text.  Anything in the block that is not such a declaration raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, re.S)
+    if not block:
+        raise ValueError('sl_api.h: no extern "C" { ... } block')
+    *decls, rest = block.group(1).split(";")
+    if rest.strip():
+        raise ValueError("sl_api.h: declaration without ';': " + " ".join(rest.split()))
+    api = {}
+    for decl in decls:
+        decl = " ".join(decl.split())
+        m = _DECL.fullmatch(decl)
+        if not m:
+            raise ValueError("sl_api.h: not a 'RET NAME(PARAMS);' declaration: " + decl)
+        ret, name, params = m.groups()
+        if name in api:
+            raise ValueError("sl_api.h: declared twice: " + name)
+        restype = None if ret.split() == ["void"] else _ctype(ret, decl, named=False)
+        params = [] if params.split() in ([], ["void"]) else params.split(",")
+        api[name] = (restype, [_ctype(p, decl, named=True) for p in params])
+    return api
+
+
+with open(API_HEADER) as _f:
+    _API = parse_api(_f.read())
+_SIGS: dict[str, list] = {name: argtypes for name, (_, argtypes) in _API.items()}
+_RESTYPE = {name: restype for name, (restype, _) in _API.items()}
 
 
 def _bind(lib, name):
     fn = getattr(lib, name)
     fn.argtypes = _SIGS[name]
-    fn.restype = _RESTYPE.get(name, ctypes.c_int)
+    fn.restype = _RESTYPE[name]
 
 
 def available() -> bool:

@@ -15,46 +15,6 @@ import torch
 
 from . import _native as N
 
-P, I, L, F = N.P, N.I, N.L, N.F
-
-N.register("sl_conv_fwd", [P, I, I, I, I, P, I, I, I, I, I, I, I, P, I, P, P, P, P])
-N.register("sl_conv_dgrad", [P, I, I, I, I, P, I, I, I, I, I, I, I, P, P, P])
-N.register("sl_conv_dgrad_bnx", [P, I, I, I, I, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, I, P])
-N.register("sl_conv_dgrad_s2_even", [P, I, I, I, I, P, I, I, I, P, P])
-N.register("sl_conv_wgrad", [P, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, P, L, P])
-N.register("sl_conv_wgrad_ws_need", [], ctypes.c_long)
-N.register("sl_conv_wt", [P, I, L, P])
-N.register("sl_conv_wt_desc_size", [])
-N.register("sl_input_norm", [P, P, P, I, I, L, P, P, F, F, F, F, F, F, P])
-N.register("sl_input_aug", [P, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, P, P, F, F, F, F, F, F, P])
-N.register("sl_input_mix", [P, P, P, I, I, I, I, I, I, ctypes.c_ulonglong, P, I, P, P, P, P, F, F, F, F, F, F, P])
-N.register("sl_cursor_bump", [P, P])
-N.register("sl_bn_finalize", [P, P, P, P, P, P, I, F, F, F, P])
-N.register("sl_bn_apply", [P, P, P, P, P, L, I, I, I, P])
-N.register("sl_bn_bwd_reduce", [P, P, P, P, P, P, P, P, P, L, I, P])
-N.register("sl_bn_bwd_finalize", [P, P, P, P, P, I, F, P])
-N.register("sl_bn_bwd_apply", [P, P, P, P, P, L, I, P])
-N.register("sl_rsum_floats", [I], ctypes.c_long)
-N.register("sl_rsum_result_offset", [I], ctypes.c_long)
-N.register("sl_conv_set_s2", [I])
-N.register("sl_bn_apply_stats", [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, F, F, F, P])
-N.register("sl_bn_bwd_apply_sums", [P, P, P, P, P, P, P, P, P, L, I, F, P])
-N.register("sl_bn_bwd_apply_dual", [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, F, P])
-N.register("sl_maxpool_fwd", [P, P, P, I, I, I, I, I, I, I, I, I, P])
-N.register("sl_maxpool_bwd", [P, P, P, I, I, I, I, I, I, I, I, I, P])
-N.register("sl_avgpool_fwd", [P, P, I, I, I, P])
-N.register("sl_avgpool_bwd", [P, P, I, I, I, P])
-N.register("sl_softmax_ce", [P, P, P, P, P, I, P, I, I, F, P])
-N.register("sl_softmax_ce_soft", [P, P, P, P, P, I, P, I, I, F, P, F, P])
-N.register("sl_softmax_ce_wide", [P, P, P, P, P, I, P, I, I, F, P, F, I, P, L, P])
-N.register("sl_softmax_ce_wide_ws_floats", [I, I], ctypes.c_long)
-N.register("sl_wgrad_side_begin", [P])
-N.register("sl_wgrad_side_join", [P, I])
-N.register("sl_conv3x3_c64_applicable", [I, I, I, I, I, I, I, I, I])
-N.register("sl_conv3x3_bnin_fwd", [P, P, I, I, P, I, P, P, P, P, P, P, P, F, F, F, P])
-N.register("sl_conv3x3_bnin_wgrad", [P, P, I, I, P, P, L, P, P, P, F, F, P])
-N.register("sl_conv_kernels_seen", [I])
-
 # bit i of sl_conv_kernels_seen = family i (csrc/kernels/common.h SlConvFamily, same order)
 KERNEL_FAMILIES = (
     "gemm_64x64", "gemm_64x128", "gemm_128x64", "gemm_128x128",

@@ -2,19 +2,10 @@
 top-k sparse select / scatter (csrc/kernels/gossip_sparse.hip)."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native as N
-
-N.register("sl_gossip_apply", [N.P, N.P, N.P, N.L, ctypes.c_double, N.P, N.L, N.P])
-N.register("sl_gossip_absorb", [N.P, N.P, N.P, N.L, ctypes.c_double, N.P, N.L, N.L, N.P])
-# top-k sparse gossip (csrc/kernels/gossip_sparse.hip)
-N.register("sl_gossip_topk_workspace", [N.L], restype=ctypes.c_long)
-N.register("sl_gossip_topk", [N.P, N.P, N.L, N.L, N.P, N.P, N.P, N.P, N.P])
-N.register("sl_gossip_scatter", [N.P, N.P, N.P, N.P, N.L, N.L, ctypes.c_double, N.I, N.P])
 
 
 def delta_apply(model: torch.Tensor, old: torch.Tensor, din: torch.Tensor | None, alpha: float,

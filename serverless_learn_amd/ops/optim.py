@@ -35,22 +35,6 @@ SCHEDULES = ("constant", "linear", "cosine")
 # update-kernel rules (csrc/kernels/mlp_fused.hip)
 RULE_SGD, RULE_SGD_LR, RULE_ADAMW = 0, 1, 2
 
-N.register("sl_sgd_flat", [N.P, N.P, N.P, N.P, N.L, N.F, N.F, N.F, N.F, N.P])
-N.register("sl_to_bf16", [N.P, N.P, N.L, N.P])
-_ADAM = [N.F] * 7  # beta1, beta2, 1 - beta1, 1 - beta2, ln beta1, ln beta2, eps
-N.register("sl_adamw_flat", [N.P, N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, N.F, *_ADAM, N.P])
-N.register("sl_sgd_flat_lr", [N.P, N.P, N.P, N.P, N.L, N.P, N.P, N.I, N.F, N.F, N.F, N.P])
-_STEP = [N.P, N.P, N.P, N.I]  # step, ticket, lr table, its length
-N.register("sl_clip_grad_partials", [N.L])
-N.register("sl_clip_grad_norm", [N.P, N.L, N.F, N.P, N.I, N.P, N.P])
-N.register("sl_accum_flat", [N.P, N.P, N.L, N.I, N.P])
-N.register("sl_ema_flat", [N.P, N.P, N.L, N.P, N.P, N.P, N.I, N.P])
-N.register("sl_cursor_bump", [N.P, N.P])  # (ops/cnn.py's launcher: the MLP's accumulated step bumps its cursor with it)
-N.register("sl_mlp_opt", [N.I, N.P, N.P, N.P, N.P, N.I, N.L, N.P, N.F, N.F, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P,
-                          N.P, N.P, *_STEP, *_ADAM, N.P])
-N.register("sl_mlp_opt_xgmi", [N.I, N.P, N.P, N.P, N.F, N.F, N.F, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.P, N.L, N.I,
-                               N.I, N.L, N.P, N.I, *_STEP, *_ADAM, N.P])
-
 
 # ---- semantics ----
 def lr_at(step: int, lr: float, schedule: str = "constant", warmup_steps: int = 0, decay_steps: int = 0,

@@ -42,21 +42,6 @@ import torch
 
 from ..ops import _native as N
 
-N.register("sl_xgmi_header_bytes", [])
-N.register("sl_xgmi_alloc", [N.L, ctypes.POINTER(ctypes.c_void_p)])
-N.register("sl_xgmi_free", [N.P])
-N.register("sl_ipc_get_handle", [N.P, N.P])
-N.register("sl_ipc_handle_size", [])
-N.register("sl_ipc_open", [N.P, ctypes.POINTER(ctypes.c_void_p)])
-N.register("sl_ipc_close", [N.P])
-N.register("sl_xgmi_buffer_bytes", [N.L], restype=ctypes.c_long)
-N.register("sl_xgmi_copyin", [N.P, N.P, N.L, N.I, N.I, N.L, N.P, N.L, N.P])
-N.register("sl_xgmi_barrier", [N.P, N.P, N.L, N.I, N.I, N.L, N.I, N.P])
-N.register("sl_xgmi_rs", [N.P, N.P, N.L, N.I, N.I, N.L, N.L, N.I, N.P])
-N.register("sl_xgmi_abort", [N.P, N.P])
-N.register("sl_xgmi_sum", [N.P, N.P, N.L, N.I, N.I, N.L, N.P, N.L, N.F, N.P])
-N.register("sl_xgmi_peek", [N.P, N.P, N.L, N.I, N.I, N.L, N.I, N.I, N.I, N.P, N.L, N.P])
-
 MAX_WORLD = 16
 
 
