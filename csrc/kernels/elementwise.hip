@@ -168,6 +168,100 @@ __global__ __launch_bounds__(256) void opt_flat_kernel(float* __restrict__ w, co
   }
 }
 
+// opt_flat_kernel with a weight decay per class: element i has class cls[i >> 6] (0 weight, 1 norm,
+// 2 bias; every tensor of the vector starts on a 64-element boundary, so a float4 chunk never
+// straddles two classes and a wave's 256 elements read four bytes of the map).  Class 0 decays by
+// FlatOpt's wd.  Same walk and grid; the three decays (SGD) / keep factors (AdamW) are
+// wave-uniform scalars computed once per thread.
+//
+// A sibling kernel and not a template flag of opt_flat_kernel: routing both through one inlined
+// body changed which product the compiler contracts in the ungrouped SGD rule (its float4 chunks
+// compute fma(gscale, g, wd w), its scalar tail fma(wd, w, gscale g)), and an ungrouped trainer
+// must keep its bits.  Here every contraction is written out to match that kernel, so that a
+// grouped launch leaves in each element exactly what opt_flat_kernel leaves with that class's
+// decay (tests/test_decay_groups_gpu.py compares them bit for bit).
+struct FlatGroups {
+  const uint8_t* cls;
+  float wd_norm, wd_bias;  // the decay of classes 1 and 2
+};
+
+template <bool ADAMW>
+__global__ __launch_bounds__(256) void opt_flat_groups_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                              float* __restrict__ mom, float* __restrict__ v,
+                                                              uint16_t* __restrict__ shadow, long n, FlatOpt o,
+                                                              FlatGroups gr) {
+  // wave-uniform scalars of the step, ahead of the loads
+  const int k = *o.step;
+  const float lr = o.lr_tab ? o.lr_tab[k < o.lr_last ? k : o.lr_last] : o.lr;
+  float ssz = 0.f, rbc2 = 0.f;
+  // per class: the decay (SGD) or the keep factor 1 - lr wd (AdamW)
+  float dk[3] = {o.wd, gr.wd_norm, gr.wd_bias};
+  if constexpr (ADAMW) {
+    const float t = (float)k + 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dk[c] = 1.f - lr * dk[c];
+    ssz = lr / -expm1f(t * o.lnb1);
+    rbc2 = 1.f / sqrtf(-expm1f(t * o.lnb2));
+  }
+  auto class_of = [&](long i) __attribute__((always_inline)) {
+    const int c = gr.cls[i >> 6];
+    return c == 0 ? dk[0] : c == 1 ? dk[1] : dk[2];
+  };
+  // TAIL: the scalar tail's contraction of the SGD rule (see above)
+  auto apply = [&](float& wj, float gj, float& mj, float& vj, float dkc, bool tail) __attribute__((always_inline)) {
+    if constexpr (ADAMW) {
+      const float gs = gj * o.gscale;
+      mj = fmaf(o.b1, mj, o.omb1 * gs);
+      vj = fmaf(o.b2, vj, o.omb2 * gs * gs);
+      wj = fmaf(-ssz, mj / fmaf(sqrtf(vj), rbc2, o.eps), wj * dkc);
+    } else {
+      float d = tail ? fmaf(dkc, wj, gj * o.gscale) : fmaf(gj, o.gscale, dkc * wj);
+      if (mom) { d = fmaf(o.mu, mj, d); mj = d; }
+      wj = fmaf(-lr, d, wj);
+    }
+  };
+  const long stride = (long)gridDim.x * blockDim.x * 4;
+  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      float4 wv = *reinterpret_cast<float4*>(w + i);
+      const float4 gv = *reinterpret_cast<const float4*>(g + i);
+      float wa[4] = {wv.x, wv.y, wv.z, wv.w};
+      const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
+      float ma[4] = {0.f, 0.f, 0.f, 0.f}, va[4] = {0.f, 0.f, 0.f, 0.f};
+      if (mom) {
+        const float4 mv = *reinterpret_cast<const float4*>(mom + i);
+        ma[0] = mv.x; ma[1] = mv.y; ma[2] = mv.z; ma[3] = mv.w;
+      }
+      if constexpr (ADAMW) {
+        const float4 vv = *reinterpret_cast<const float4*>(v + i);
+        va[0] = vv.x; va[1] = vv.y; va[2] = vv.z; va[3] = vv.w;
+      }
+      const float dkc = class_of(i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) apply(wa[j], ga[j], ma[j], va[j], dkc, false);
+      *reinterpret_cast<float4*>(w + i) = make_float4(wa[0], wa[1], wa[2], wa[3]);
+      if (mom) *reinterpret_cast<float4*>(mom + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+      if constexpr (ADAMW) *reinterpret_cast<float4*>(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+      if (shadow) {
+        uint2 pk;
+        pk.x = pack2(wa[0], wa[1]);
+        pk.y = pack2(wa[2], wa[3]);
+        *reinterpret_cast<uint2*>(shadow + i) = pk;
+      }
+    } else {
+      for (long q = i; q < n; ++q) {
+        float wq = w[q], mq = mom ? mom[q] : 0.f, vq = 0.f;
+        if constexpr (ADAMW) vq = v[q];
+        apply(wq, g[q], mq, vq, class_of(q), true);
+        w[q] = wq;
+        if (mom) mom[q] = mq;
+        if constexpr (ADAMW) v[q] = vq;
+        if (shadow) shadow[q] = f2bf(wq);
+      }
+    }
+  }
+}
+
 // K5c -- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) over the flat fp32
 // gradient, as two launches with no atomics and no state a graph replay would have to reset:
 //   1. clip_sumsq_kernel: grid-stride float4 walk (scalar tail for n % 4), squares accumulated
@@ -390,6 +484,41 @@ int sl_adamw_flat(float* w, const float* g, float* mom, float* v, uint16_t* shad
   if (!(lnb1 < 0.f) || !(lnb2 < 0.f) || !(eps > 0.f)) return -1;  // bias corrections divide by 1 - b^t
   const FlatOpt o = {step, lr_tab, lr_tab ? lr_n - 1 : 0, lr, 0.f, wd, gscale, b1, b2, omb1, omb2, lnb1, lnb2, eps};
   hipLaunchKernelGGL(opt_flat_kernel<true>, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom, v, shadow, n, o);
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool flat_groups_ok(const uint8_t* cls, float wd, float wd_norm, float wd_bias) {
+  return cls && wd >= 0.f && wd_norm >= 0.f && wd_bias >= 0.f;  // (NaN fails every comparison)
+}
+
+// sl_adamw_flat with a weight decay per class: element i decays by wd (cls[i >> 6] == 0), wd_norm
+// (1) or wd_bias (2).  cls: one byte per 64 elements, (n + 63) / 64 of them, each 0, 1 or 2.
+int sl_adamw_flat_groups(float* w, const float* g, float* mom, float* v, uint16_t* shadow, long n, const int* step,
+                         const float* lr_tab, int lr_n, float lr, float wd, float gscale, float b1, float b2,
+                         float omb1, float omb2, float lnb1, float lnb2, float eps, const uint8_t* cls, float wd_norm,
+                         float wd_bias, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!mom || !v || !flat_opt_ok(w, g, mom, v, shadow, step, lr_tab, lr_n)) return -1;
+  if (!(lnb1 < 0.f) || !(lnb2 < 0.f) || !(eps > 0.f) || !flat_groups_ok(cls, wd, wd_norm, wd_bias)) return -1;
+  const FlatOpt o = {step, lr_tab, lr_tab ? lr_n - 1 : 0, lr, 0.f, wd, gscale, b1, b2, omb1, omb2, lnb1, lnb2, eps};
+  hipLaunchKernelGGL(opt_flat_groups_kernel<true>, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom, v, shadow,
+                     n, o, FlatGroups{cls, wd_norm, wd_bias});
+  SL_CHECK_LAUNCH();
+  return 0;
+}
+
+// sl_sgd_flat_lr with a weight decay per class (see sl_adamw_flat_groups); without a table the
+// learning rate is lr
+int sl_sgd_flat_lr_groups(float* w, const float* g, float* mom, uint16_t* shadow, long n, const int* step,
+                          const float* lr_tab, int lr_n, float lr, float mu, float wd, float gscale,
+                          const uint8_t* cls, float wd_norm, float wd_bias, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!flat_opt_ok(w, g, mom, nullptr, shadow, step, lr_tab, lr_n) || !flat_groups_ok(cls, wd, wd_norm, wd_bias))
+    return -1;
+  const FlatOpt o = {step, lr_tab, lr_tab ? lr_n - 1 : 0, lr, mu, wd, gscale, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  hipLaunchKernelGGL(opt_flat_groups_kernel<false>, dim3(grid_for(n, 4)), dim3(256), 0, stream, w, g, mom,
+                     static_cast<float*>(nullptr), shadow, n, o, FlatGroups{cls, wd_norm, wd_bias});
   SL_CHECK_LAUNCH();
   return 0;
 }

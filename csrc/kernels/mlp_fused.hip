@@ -1753,6 +1753,9 @@ __device__ __forceinline__ float quad_sum(float v) {
 //   RULE_SGD_LR  momentum SGD, lr from the schedule table
 //   RULE_ADAMW   torch.optim.AdamW (decoupled weight decay, bias correction, no amsgrad);
 //                a.mom is the first moment, o.v the second; lr from the table or a.lr
+// GROUPS (a second compile-time parameter, of the step-counter rules only) gives the biases b1,
+// b2 and b3 a weight decay of their own: an element's class follows from its index (the ranges
+// are compile-time constants), so no map is read.
 constexpr int RULE_SGD = 0, RULE_SGD_LR = 1, RULE_ADAMW = 2;
 
 struct OptArgs {
@@ -1773,10 +1776,12 @@ struct OptStep {
   float keep;  // AdamW: 1 - lr wd
   float ssz;   // AdamW: lr / (1 - b1^t)
   float rbc2;  // AdamW: 1 / sqrt(1 - b2^t)
+  float wd_bias;    // GROUPS: the biases' weight decay
+  float keep_bias;  // GROUPS, AdamW: 1 - lr wd_bias
 };
 
-template <int RULE>
-__device__ __forceinline__ OptStep opt_begin(const SgdArgs& a, const OptArgs& o) {
+template <int RULE, bool GROUPS = false>
+__device__ __forceinline__ OptStep opt_begin(const SgdArgs& a, const OptArgs& o, float wd_bias = 0.f) {
   OptStep s = {};
   if constexpr (RULE != RULE_SGD) {
     s.k = __hip_atomic_load(o.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1786,9 +1791,16 @@ __device__ __forceinline__ OptStep opt_begin(const SgdArgs& a, const OptArgs& o)
       s.keep = 1.f - s.lr * a.wd;
       s.ssz = s.lr / -expm1f(t * o.lnb1);
       s.rbc2 = 1.f / sqrtf(-expm1f(t * o.lnb2));
+      if constexpr (GROUPS) s.keep_bias = 1.f - s.lr * wd_bias;
     }
+    if constexpr (GROUPS) s.wd_bias = wd_bias;
   }
   return s;
+}
+
+// GROUPS: whether parameter p is a bias (b1, b2 or b3)
+__device__ __forceinline__ bool is_bias(long p) {
+  return (p >= P_B1 && p < P_W2) || (p >= P_B2 && p < P_W3) || p >= P_B3;
 }
 
 // Every workgroup read the step at its start (opt_begin); the one that draws the last ticket
@@ -1810,21 +1822,30 @@ __device__ __forceinline__ void opt_end(const OptArgs& o, const OptStep& s) {
 
 // w0 / m0 / v0: the parameter and its optimizer state, loaded by the caller ahead of the slab
 // sums.  The single place the rule lives.  Returns write_shadow's fixed-point fp16 W1 value.
-template <int RULE>
+template <int RULE, bool GROUPS = false>
 __device__ __forceinline__ long long sgd_apply(const SgdArgs& a, const OptArgs& o, const OptStep& s, float* gout,
                                                long p, float gme, float w0, float m0, float v0) {
+  static_assert(!GROUPS || RULE != RULE_SGD, "decay groups run under the step-counter rules");
   if (gout) gout[p] = gme;
   if (a.mode == 1) return 0;
   float w = w0;
+  // the decay (SGD) / keep factor (AdamW) of this element's class
+  float wd = a.wd, keep = s.keep;
+  if constexpr (GROUPS) {
+    if (is_bias(p)) {
+      wd = s.wd_bias;
+      keep = s.keep_bias;
+    }
+  }
   if constexpr (RULE == RULE_ADAMW) {
     // explicit fma: the same bits from every kernel that carries the rule
     const float m = fmaf(o.b1, m0, o.omb1 * gme);
     const float v = fmaf(o.b2, v0, o.omb2 * gme * gme);
     a.mom[p] = m;
     o.v[p] = v;
-    w = fmaf(-s.ssz, m / fmaf(sqrtf(v), s.rbc2, o.eps), w0 * s.keep);
+    w = fmaf(-s.ssz, m / fmaf(sqrtf(v), s.rbc2, o.eps), w0 * keep);
   } else {
-    float d = gme + a.wd * w;
+    float d = gme + wd * w;
     if (a.mom) {
       d = a.mu * m0 + d;
       a.mom[p] = d;
@@ -1852,7 +1873,7 @@ __device__ __forceinline__ float group_sum(float v) {
 // single parameters).  w / mom / the shadows are then touched in a scattered order, but they
 // are 1 MB arrays that stay in L2.
 // Returns this thread's fixed-point fp16 W1 weight (mode 2), for the row sums.
-template <int RULE>
+template <int RULE, bool GROUPS = false>
 __device__ __forceinline__ long long sgd_tiled(const SgdArgs& a, const OptArgs& o, const OptStep& os, long u,
                                                int part) {
   const long off = u * 4;
@@ -1917,7 +1938,7 @@ __device__ __forceinline__ long long sgd_tiled(const SgdArgs& a, const OptArgs& 
   if (!mine) return 0;
   float* gout = a.grad_out;
   if (a.ar_ctl && (xg_cur(a.ar_ctl, a.xg.inline_sync) & 1u)) gout = a.grad_out_alt;
-  return sgd_apply<RULE>(a, o, os, gout, pe, gme, w0, m0, v0);
+  return sgd_apply<RULE, GROUPS>(a, o, os, gout, pe, gme, w0, m0, v0);
 }
 
 // float4 units a launch of mlp_sgd_kernel walks: the slab's (tiled) or the parameters'
@@ -1925,14 +1946,14 @@ __host__ __device__ constexpr long sgd_units(bool slab) {
   return slab ? TL_STRIDE / 4 : (P_N + 3) / 4;
 }
 
-template <int RULE>
+template <int RULE, bool GROUPS = false>
 __device__ __forceinline__ void mlp_sgd_body(const SgdArgs& a, const OptArgs& o, const OptStep& os) {
   if (a.cursor && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.cursor, 1);
   if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 2] = __builtin_amdgcn_s_memrealtime();
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int part = (int)(t % SGD_TPG);
   if (a.slab && a.mode != 0) {
-    const long long fx = sgd_tiled<RULE>(a, o, os, t / SGD_TPG, part);
+    const long long fx = sgd_tiled<RULE, GROUPS>(a, o, os, t / SGD_TPG, part);
     // W1 row sums: a workgroup of the tiled walk covers 128 units of one tile = 16 rows
     // (m_base + lane & 15) x 32 columns (one R1 block) of W1; its 512 fixed-point values are
     // summed per row in LDS (integer: order-free, exact) and written as that block's partials
@@ -1976,7 +1997,7 @@ __device__ __forceinline__ void mlp_sgd_body(const SgdArgs& a, const OptArgs& o,
   if (a.ar_ctl && (xg_cur(a.ar_ctl, a.xg.inline_sync) & 1u)) gout = a.grad_out_alt;
   float v0 = 0.f;
   if constexpr (RULE == RULE_ADAMW) v0 = upd ? o.v[p] : 0.f;
-  sgd_apply<RULE>(a, o, os, gout, p, gme, w0, m0, v0);
+  sgd_apply<RULE, GROUPS>(a, o, os, gout, p, gme, w0, m0, v0);
 }
 
 __global__ __launch_bounds__(SGD_NT) void mlp_sgd_kernel(SgdArgs a) {
@@ -1988,6 +2009,14 @@ template <int RULE>
 __global__ __launch_bounds__(SGD_NT) void mlp_opt_kernel(SgdArgs a, OptArgs o) {
   const OptStep os = opt_begin<RULE>(a, o);
   mlp_sgd_body<RULE>(a, o, os);
+  opt_end(o, os);
+}
+
+// ... with the biases' own weight decay (the ungrouped kernel keeps its name and parameter list)
+template <int RULE>
+__global__ __launch_bounds__(SGD_NT) void mlp_opt_groups_kernel(SgdArgs a, OptArgs o, float wd_bias) {
+  const OptStep os = opt_begin<RULE, true>(a, o, wd_bias);
+  mlp_sgd_body<RULE, true>(a, o, os);
   opt_end(o, os);
 }
 
@@ -2028,7 +2057,7 @@ __device__ __forceinline__ float4 xg_load_reduced_any(const XgArgs& x, unsigned 
   return owner == lo ? va : vb;
 }
 
-template <bool XG, int RULE>
+template <bool XG, int RULE, bool GROUPS = false>
 __device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& x, const OptArgs& o,
                                                 const OptStep& os) {
   __shared__ unsigned s_step;
@@ -2096,7 +2125,7 @@ __device__ __forceinline__ void mlp_update_body(const SgdArgs& a, const XgArgs& 
       const float va[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (i4 * 4 + j < P_N) fx += sgd_apply<RULE>(a, o, os, nullptr, i4 * 4 + j, ga[j], wa[j], ma[j], va[j]);
+        if (i4 * 4 + j < P_N) fx += sgd_apply<RULE, GROUPS>(a, o, os, nullptr, i4 * 4 + j, ga[j], wa[j], ma[j], va[j]);
     }
     if (w1) {  // 32-column block b = lanes 8b .. 8b+7 of the row (the 25th: 4 live lanes + 4 dead)
       fx += __shfl_xor(fx, 1);
@@ -2120,6 +2149,13 @@ template <bool XG, int RULE>
 __global__ __launch_bounds__(UPD_NT) void mlp_opt_update_kernel(SgdArgs a, XgArgs x, OptArgs o) {
   const OptStep os = opt_begin<RULE>(a, o);
   mlp_update_body<XG, RULE>(a, x, o, os);
+  opt_end(o, os);
+}
+
+template <bool XG, int RULE>
+__global__ __launch_bounds__(UPD_NT) void mlp_opt_update_groups_kernel(SgdArgs a, XgArgs x, OptArgs o, float wd_bias) {
+  const OptStep os = opt_begin<RULE, true>(a, o, wd_bias);
+  mlp_update_body<XG, RULE, true>(a, x, o, os);
   opt_end(o, os);
 }
 
@@ -2350,12 +2386,13 @@ int sl_mlp_sgd(float* w, float* mom, const float* slab, int slices, long slab_st
 }
 
 // The rules that read the optimizer step (RULE_SGD_LR / RULE_ADAMW): their arguments, checked.
+// groups: the grouped entry points, where RULE_SGD_LR without a table runs at the scalar lr
 static bool opt_fill(OptArgs& o, int rule, const float* mom, float* v, int* step, unsigned* ticket,
                      const float* lr_tab, int lr_n, float b1, float b2, float omb1, float omb2, float lnb1,
-                     float lnb2, float eps) {
+                     float lnb2, float eps, bool groups = false) {
   if (rule != RULE_SGD_LR && rule != RULE_ADAMW) return false;
   if (!step || !ticket) return false;
-  if (lr_tab ? lr_n < 1 : rule == RULE_SGD_LR) return false;  // scheduled SGD has no scalar-lr form here
+  if (lr_tab ? lr_n < 1 : rule == RULE_SGD_LR && !groups) return false;  // ungrouped SGD at a scalar lr: sl_mlp_sgd
   if (rule == RULE_ADAMW) {
     if (!mom || !v || ((uintptr_t)v & 15)) return false;
     if (!(lnb1 < 0.f) || !(lnb2 < 0.f) || !(eps > 0.f)) return false;  // bias corrections divide by 1 - b^t
@@ -2369,11 +2406,13 @@ static bool opt_fill(OptArgs& o, int rule, const float* mom, float* v, int* step
 // slab (slab != nullptr: reduction + update in one launch) or from an aggregated gradient
 // (grad_in).  mom is AdamW's first moment, v its second; lr_tab[min(step, lr_n - 1)] is the
 // step's learning rate (nullptr: lr).  The launch advances *step by one (opt_end).
-int sl_mlp_opt(int rule, float* w, float* mom, float* v, const float* slab, int slices, long slab_stride,
-               const float* grad_in, float lr, float mu, float wd, float xa, float xb, uint16_t* w1h,
-               uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, long long* r1p,
-               int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1,
-               float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+// groups: the biases b1, b2, b3 decay by wd_bias instead of wd (sl_mlp_opt_groups)
+static int mlp_opt_launch(bool groups, float wd_bias, int rule, float* w, float* mom, float* v, const float* slab,
+                          int slices, long slab_stride, const float* grad_in, float lr, float mu, float wd, float xa,
+                          float xb, uint16_t* w1h, uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th,
+                          int* cursor, long long* r1p, int* step, unsigned* ticket, const float* lr_tab, int lr_n,
+                          float b1, float b2, float omb1, float omb2, float lnb1, float lnb2, float eps,
+                          hipStream_t stream) {
   SgdArgs a = {};
   a.w = w; a.mom = mom; a.slab = slab; a.slices = slices; a.slab_stride = slab_stride;
   a.grad_in = grad_in; a.n = P_N; a.lr = lr; a.mu = mu; a.wd = wd; a.mode = 2;
@@ -2381,25 +2420,57 @@ int sl_mlp_opt(int rule, float* w, float* mom, float* v, const float* slab, int 
   a.w1h = w1h; a.w2h = w2h; a.w2th = w2th; a.w3h = w3h; a.w3th = w3th; a.cursor = cursor;
   a.r1p = r1p; a.stamps = g_sgd_stamps;
   OptArgs o = {};
-  if (!opt_fill(o, rule, mom, v, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps)) return -1;
+  if (!opt_fill(o, rule, mom, v, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps, groups)) return -1;
+  if (groups && !(wd >= 0.f && wd_bias >= 0.f)) return -1;  // (NaN fails the comparison)
   if (!w || !r1p || (!slab == !grad_in)) return -1;
   if (slab && ((slab_stride & 3) || slab_stride < TL_STRIDE)) return -1;
   if (!slab) {
     if (((uintptr_t)w | (uintptr_t)grad_in | (uintptr_t)(mom ? mom : w)) & 15) return -2;
-    if (rule == RULE_ADAMW)
-      hipLaunchKernelGGL((mlp_opt_update_kernel<false, RULE_ADAMW>), dim3(UPD_TASKS), dim3(UPD_NT), 0, stream, a,
-                         XgArgs{}, o);
+    const dim3 grid(UPD_TASKS), block(UPD_NT);
+    if (groups && rule == RULE_ADAMW)
+      hipLaunchKernelGGL((mlp_opt_update_groups_kernel<false, RULE_ADAMW>), grid, block, 0, stream, a, XgArgs{}, o,
+                         wd_bias);
+    else if (groups)
+      hipLaunchKernelGGL((mlp_opt_update_groups_kernel<false, RULE_SGD_LR>), grid, block, 0, stream, a, XgArgs{}, o,
+                         wd_bias);
+    else if (rule == RULE_ADAMW)
+      hipLaunchKernelGGL((mlp_opt_update_kernel<false, RULE_ADAMW>), grid, block, 0, stream, a, XgArgs{}, o);
     else
-      hipLaunchKernelGGL((mlp_opt_update_kernel<false, RULE_SGD_LR>), dim3(UPD_TASKS), dim3(UPD_NT), 0, stream, a,
-                         XgArgs{}, o);
+      hipLaunchKernelGGL((mlp_opt_update_kernel<false, RULE_SGD_LR>), grid, block, 0, stream, a, XgArgs{}, o);
     SL_CHECK_LAUNCH();
     return 0;
   }
   const dim3 grid((sgd_units(true) * SGD_TPG + SGD_NT - 1) / SGD_NT);
-  if (rule == RULE_ADAMW) hipLaunchKernelGGL(mlp_opt_kernel<RULE_ADAMW>, grid, dim3(SGD_NT), 0, stream, a, o);
+  if (groups && rule == RULE_ADAMW)
+    hipLaunchKernelGGL(mlp_opt_groups_kernel<RULE_ADAMW>, grid, dim3(SGD_NT), 0, stream, a, o, wd_bias);
+  else if (groups)
+    hipLaunchKernelGGL(mlp_opt_groups_kernel<RULE_SGD_LR>, grid, dim3(SGD_NT), 0, stream, a, o, wd_bias);
+  else if (rule == RULE_ADAMW) hipLaunchKernelGGL(mlp_opt_kernel<RULE_ADAMW>, grid, dim3(SGD_NT), 0, stream, a, o);
   else hipLaunchKernelGGL(mlp_opt_kernel<RULE_SGD_LR>, grid, dim3(SGD_NT), 0, stream, a, o);
   SL_CHECK_LAUNCH();
   return 0;
+}
+
+int sl_mlp_opt(int rule, float* w, float* mom, float* v, const float* slab, int slices, long slab_stride,
+               const float* grad_in, float lr, float mu, float wd, float xa, float xb, uint16_t* w1h,
+               uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, long long* r1p,
+               int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1,
+               float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+  return mlp_opt_launch(false, 0.f, rule, w, mom, v, slab, slices, slab_stride, grad_in, lr, mu, wd, xa, xb, w1h, w2h,
+                        w2th, w3h, w3th, cursor, r1p, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps,
+                        stream);
+}
+
+// sl_mlp_opt with the biases' own weight decay wd_bias (b1, b2 and b3; every other parameter keeps
+// wd).  RULE_SGD_LR without a table runs at lr: a grouped trainer has no plain rule.
+int sl_mlp_opt_groups(int rule, float* w, float* mom, float* v, const float* slab, int slices, long slab_stride,
+                      const float* grad_in, float lr, float mu, float wd, float xa, float xb, uint16_t* w1h,
+                      uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, long long* r1p,
+                      int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1,
+                      float omb2, float lnb1, float lnb2, float eps, float wd_bias, hipStream_t stream) {
+  return mlp_opt_launch(true, wd_bias, rule, w, mom, v, slab, slices, slab_stride, grad_in, lr, mu, wd, xa, xb, w1h,
+                        w2h, w2th, w3h, w3th, cursor, r1p, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2,
+                        eps, stream);
 }
 
 static bool xg_fill(XgArgs& x, char* const* bases, unsigned* ctl, long slot_bytes, int rank, int world, long chunk4,
@@ -2452,27 +2523,57 @@ int sl_mlp_sgd_xgmi(float* w, float* mom, float lr, float mu, float wd, uint16_t
 }
 
 // sl_mlp_sgd_xgmi under a rule that reads the optimizer step (arguments as sl_mlp_opt's)
-int sl_mlp_opt_xgmi(int rule, float* w, float* mom, float* v, float lr, float mu, float wd, uint16_t* w1h,
-                    uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, char* const* bases,
-                    unsigned* ctl, long slot_bytes, int rank, int world, long chunk4, long long* r1p,
-                    int inline_sync, int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1,
-                    float b2, float omb1, float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+static int mlp_opt_xgmi_launch(bool groups, float wd_bias, int rule, float* w, float* mom, float* v, float lr, float mu,
+                               float wd, uint16_t* w1h, uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th,
+                               int* cursor, char* const* bases, unsigned* ctl, long slot_bytes, int rank, int world,
+                               long chunk4, long long* r1p, int inline_sync, int* step, unsigned* ticket,
+                               const float* lr_tab, int lr_n, float b1, float b2, float omb1, float omb2, float lnb1,
+                               float lnb2, float eps, hipStream_t stream) {
   if (!r1p || !w) return -1;
   if (((uintptr_t)w | (uintptr_t)(mom ? mom : w)) & 15) return -2;
   SgdArgs a = {};
   a.w = w; a.mom = mom; a.n = P_N; a.lr = lr; a.mu = mu; a.wd = wd; a.mode = 2;
   a.w1h = w1h; a.w2h = w2h; a.w2th = w2th; a.w3h = w3h; a.w3th = w3th; a.cursor = cursor; a.r1p = r1p;
   OptArgs o = {};
-  if (!opt_fill(o, rule, mom, v, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps)) return -1;
+  if (!opt_fill(o, rule, mom, v, step, ticket, lr_tab, lr_n, b1, b2, omb1, omb2, lnb1, lnb2, eps, groups)) return -1;
+  if (groups && !(wd >= 0.f && wd_bias >= 0.f)) return -1;  // (NaN fails the comparison)
   XgArgs x;
   if (!xg_fill(x, bases, ctl, slot_bytes, rank, world, chunk4, inline_sync)) return -1;
   const int grid = inline_sync == 2 ? xg_shared_grid(UPD_TASKS, world) : UPD_TASKS;
-  if (rule == RULE_ADAMW)
+  if (groups && rule == RULE_ADAMW)
+    hipLaunchKernelGGL((mlp_opt_update_groups_kernel<true, RULE_ADAMW>), dim3(grid), dim3(UPD_NT), 0, stream, a, x, o,
+                       wd_bias);
+  else if (groups)
+    hipLaunchKernelGGL((mlp_opt_update_groups_kernel<true, RULE_SGD_LR>), dim3(grid), dim3(UPD_NT), 0, stream, a, x, o,
+                       wd_bias);
+  else if (rule == RULE_ADAMW)
     hipLaunchKernelGGL((mlp_opt_update_kernel<true, RULE_ADAMW>), dim3(grid), dim3(UPD_NT), 0, stream, a, x, o);
   else
     hipLaunchKernelGGL((mlp_opt_update_kernel<true, RULE_SGD_LR>), dim3(grid), dim3(UPD_NT), 0, stream, a, x, o);
   SL_CHECK_LAUNCH();
   return 0;
+}
+
+int sl_mlp_opt_xgmi(int rule, float* w, float* mom, float* v, float lr, float mu, float wd, uint16_t* w1h,
+                    uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, char* const* bases,
+                    unsigned* ctl, long slot_bytes, int rank, int world, long chunk4, long long* r1p,
+                    int inline_sync, int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1,
+                    float b2, float omb1, float omb2, float lnb1, float lnb2, float eps, hipStream_t stream) {
+  return mlp_opt_xgmi_launch(false, 0.f, rule, w, mom, v, lr, mu, wd, w1h, w2h, w2th, w3h, w3th, cursor, bases, ctl,
+                             slot_bytes, rank, world, chunk4, r1p, inline_sync, step, ticket, lr_tab, lr_n, b1, b2,
+                             omb1, omb2, lnb1, lnb2, eps, stream);
+}
+
+// sl_mlp_opt_xgmi with the biases' own weight decay (see sl_mlp_opt_groups)
+int sl_mlp_opt_xgmi_groups(int rule, float* w, float* mom, float* v, float lr, float mu, float wd, uint16_t* w1h,
+                           uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor,
+                           char* const* bases, unsigned* ctl, long slot_bytes, int rank, int world, long chunk4,
+                           long long* r1p, int inline_sync, int* step, unsigned* ticket, const float* lr_tab,
+                           int lr_n, float b1, float b2, float omb1, float omb2, float lnb1, float lnb2, float eps,
+                           float wd_bias, hipStream_t stream) {
+  return mlp_opt_xgmi_launch(true, wd_bias, rule, w, mom, v, lr, mu, wd, w1h, w2h, w2th, w3h, w3th, cursor, bases,
+                             ctl, slot_bytes, rank, world, chunk4, r1p, inline_sync, step, ticket, lr_tab, lr_n, b1,
+                             b2, omb1, omb2, lnb1, lnb2, eps, stream);
 }
 
 }  // extern "C"

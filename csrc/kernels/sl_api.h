@@ -148,6 +148,13 @@ int sl_adamw_flat(float* w, const float* g, float* mom, float* v, uint16_t* shad
                   float omb2, float lnb1, float lnb2, float eps, hipStream_t stream);
 int sl_sgd_flat_lr(float* w, const float* g, float* mom, uint16_t* shadow, long n, const int* step,
                    const float* lr_tab, int lr_n, float mu, float wd, float gscale, hipStream_t stream);
+int sl_adamw_flat_groups(float* w, const float* g, float* mom, float* v, uint16_t* shadow, long n, const int* step,
+                         const float* lr_tab, int lr_n, float lr, float wd, float gscale, float b1, float b2,
+                         float omb1, float omb2, float lnb1, float lnb2, float eps, const uint8_t* cls, float wd_norm,
+                         float wd_bias, hipStream_t stream);
+int sl_sgd_flat_lr_groups(float* w, const float* g, float* mom, uint16_t* shadow, long n, const int* step,
+                          const float* lr_tab, int lr_n, float lr, float mu, float wd, float gscale,
+                          const uint8_t* cls, float wd_norm, float wd_bias, hipStream_t stream);
 int sl_clip_grad_partials(long n);
 int sl_clip_grad_norm(float* g, long n, float max_norm, double* partials, int n_partials, float* norm_out,
                       hipStream_t stream);
@@ -208,6 +215,11 @@ int sl_mlp_opt(int rule, float* w, float* mom, float* v, const float* slab, int 
                uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, long long* r1p, int* step,
                unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1, float omb2,
                float lnb1, float lnb2, float eps, hipStream_t stream);
+int sl_mlp_opt_groups(int rule, float* w, float* mom, float* v, const float* slab, int slices, long slab_stride,
+                      const float* grad_in, float lr, float mu, float wd, float xa, float xb, uint16_t* w1h,
+                      uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor, long long* r1p,
+                      int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1,
+                      float omb2, float lnb1, float lnb2, float eps, float wd_bias, hipStream_t stream);
 int sl_mlp_reduce_xgmi(const float* slab, int slices, long slab_stride, float xa, float xb, float* slot0,
                        float* slot1, char* const* bases, unsigned* ctl, long slot_bytes, int rank, int world,
                        long chunk4, int inline_sync, hipStream_t stream);
@@ -219,6 +231,12 @@ int sl_mlp_opt_xgmi(int rule, float* w, float* mom, float* v, float lr, float mu
                     unsigned* ctl, long slot_bytes, int rank, int world, long chunk4, long long* r1p, int inline_sync,
                     int* step, unsigned* ticket, const float* lr_tab, int lr_n, float b1, float b2, float omb1,
                     float omb2, float lnb1, float lnb2, float eps, hipStream_t stream);
+int sl_mlp_opt_xgmi_groups(int rule, float* w, float* mom, float* v, float lr, float mu, float wd, uint16_t* w1h,
+                           uint16_t* w2h, uint16_t* w2th, uint16_t* w3h, uint16_t* w3th, int* cursor,
+                           char* const* bases, unsigned* ctl, long slot_bytes, int rank, int world, long chunk4,
+                           long long* r1p, int inline_sync, int* step, unsigned* ticket, const float* lr_tab,
+                           int lr_n, float b1, float b2, float omb1, float omb2, float lnb1, float lnb2, float eps,
+                           float wd_bias, hipStream_t stream);
 
 // xgmi.hip
 int sl_xgmi_header_bytes();

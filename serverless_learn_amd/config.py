@@ -62,6 +62,8 @@ class Config:
     lr: float = 0.05
     momentum: float = 0.9
     weight_decay: float = 0.0
+    norm_weight_decay: float = -1.0    # resnet18: weight decay of the BatchNorm scales and shifts; -1 = weight_decay
+    bias_weight_decay: float = -1.0    # weight decay of the other biases (fc.bias; the MLP's b1 b2 b3); -1 = weight_decay
     optimizer: str = "sgd"             # sgd (momentum SGD) | adamw (beta1, beta2, adam_eps; decoupled weight_decay)
     beta1: float = 0.9
     beta2: float = 0.999
@@ -117,10 +119,11 @@ class Config:
 
     def validate(self) -> None:
         """Refuse combinations no component implements (gradient accumulation's, the weight EMA's,
-        the input pipeline's, the soft-target loss's, held-out evaluation's and the top-k sparse
-        gossip's)."""
+        the decay groups', the input pipeline's, the soft-target loss's, held-out evaluation's and the
+        top-k sparse gossip's)."""
         self._validate_eval()
         self._validate_classes()
+        self._validate_decay_groups()
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
         if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:
@@ -159,6 +162,24 @@ class Config:
             raise ValueError("gossip_topk: the simulate model is growable and is never sparse")
         if self.gossip_compat:
             raise ValueError("gossip_topk: gossip_compat reproduces the reference's dense exchange byte for byte")
+
+    def _validate_decay_groups(self) -> None:
+        for name in ("norm_weight_decay", "bias_weight_decay"):
+            v = getattr(self, name)
+            if v == -1:
+                continue
+            if isinstance(v, bool) or not (math.isfinite(v) and v >= 0):  # NaN included
+                raise ValueError(f"{name} must be -1 (follow weight_decay) or a finite number >= 0, got {v!r}")
+            if self.model == "simulate":
+                raise ValueError(f"{name}: the simulate model has no optimizer")
+        if self.norm_weight_decay != -1 and self.model == "mlp":
+            raise ValueError("norm_weight_decay: the mlp model has no normalisation layer (model='resnet18')")
+
+    @property
+    def decay_groups(self) -> dict:
+        """The trainers' ``norm_weight_decay=`` / ``bias_weight_decay=`` keywords: those that are set
+        (-1 is None, the trainers' "follow weight_decay", and is left out)."""
+        return {k: float(getattr(self, k)) for k in ("norm_weight_decay", "bias_weight_decay") if getattr(self, k) != -1}
 
     def _validate_classes(self) -> None:
         v = self.classes

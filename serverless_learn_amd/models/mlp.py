@@ -308,6 +308,7 @@ class FusedMLPTrainer(GraphedStep, TrainerState):
 
     tickets = ("opt_ticket", "ema_ticket")  # (mlp_fused.hip opt_end; elementwise.hip sl_ema_flat)
     opt_kernels = ("sl_mlp_opt", "sl_mlp_opt_xgmi")
+    group_kernels = ("sl_mlp_opt_groups", "sl_mlp_opt_xgmi_groups")
     accum_kernels = (*ACCUM_KERNELS, "sl_cursor_bump")
 
     def layout(self):
@@ -370,12 +371,14 @@ class FusedMLPTrainer(GraphedStep, TrainerState):
         """Change optimizer hyper-parameters (OptSpec fields; ``clip_grad_norm`` under any rule,
         the others of a step-counter rule): the launches are rebuilt and the captured graphs
         dropped, as a new ``lr`` does.  The rule itself (which state exists) is fixed at
-        construction."""
+        construction, and so is whether the decay groups are on (their values may change)."""
         import dataclasses
 
         if self.opt.plain:  # a plain rule's lr / momentum / weight_decay live in the attributes
             kw = {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay, **kw}
         new = dataclasses.replace(self.opt, **kw)
+        if new.grouped != self.opt.grouped:  # (it would also change the rule: a grouped trainer is never plain)
+            raise ValueError("decay groups are switched on or off at construction (build a new trainer)")
         if (new.adamw, new.plain) != (self.opt.adamw, self.opt.plain):
             raise ValueError("the optimizer rule is fixed at construction (build a new trainer)")
         if new.emas != self.opt.emas:
@@ -419,16 +422,19 @@ class FusedMLPTrainer(GraphedStep, TrainerState):
                               p(self.h1t), p(self.dh2t), p(self.dh1t), p(self.w3p), self.w3p.shape[0], p(self.slab),
                               self.slices, self.slab_stride, entry="sl_mlp_wgrad" + sfx),
         }
+        # decay groups: the biases' own weight decay, through the grouped entry points (the MLP has no
+        # normalisation layer, so norm_weight_decay has nothing to act on)
+        gsfx, gargs = ("_groups", (self.opt.decays()[2],)) if self.opt.grouped else ("", ())
         # the update kernel's three forms: the fused "sgd" (the slab reduced and applied), the "reduce"
         # of the slab into grad (rule-independent; no cursor bump) and the "update" from grad
         for name, from_grad in (("sgd", False), ("reduce", False), ("update", True)):
             slab, gin = (None, p(self.grad)) if from_grad else (p(self.slab), None)
             reduce = name == "reduce"
             if not reduce and not self.opt.plain:  # under a step-counter rule
-                lc[name] = n.Launch("sl_mlp_opt", self.opt.rule, p(self.params), p(self.mom), p(self.v),
+                lc[name] = n.Launch("sl_mlp_opt" + gsfx, self.opt.rule, p(self.params), p(self.mom), p(self.v),
                                     slab, self.slices, self.slab_stride, gin, self.lr, self.momentum,
                                     self.weight_decay, *self.dw1_coeffs, *ws, p(self.cursor), p(self.r1p),
-                                    *self._opt_args())
+                                    *self._opt_args(), *gargs)
                 continue
             lc[name] = n.Launch("sl_mlp_sgd", p(self.params), p(self.mom), slab, self.slices, self.slab_stride,
                                 gin, p(self.grad) if reduce else None, self.lr, self.momentum, self.weight_decay,
@@ -461,9 +467,9 @@ class FusedMLPTrainer(GraphedStep, TrainerState):
                                          self.weight_decay, *ws, p(self.cursor), *xg.args(), p(self.r1p),
                                          xg.inline_sync)
             else:
-                lc["xupdate"] = n.Launch("sl_mlp_opt_xgmi", self.opt.rule, p(self.params), p(self.mom), p(self.v),
+                lc["xupdate"] = n.Launch("sl_mlp_opt_xgmi" + gsfx, self.opt.rule, p(self.params), p(self.mom), p(self.v),
                                          self.lr, self.momentum, self.weight_decay, *ws, p(self.cursor), *xg.args(),
-                                         p(self.r1p), xg.inline_sync, *self._opt_args())
+                                         p(self.r1p), xg.inline_sync, *self._opt_args(), *gargs)
         self._lc, self._lkey = lc, key
         return lc
 

@@ -264,6 +264,10 @@ class ResNetModel:
     def layout(self):
         return spec_layout(self.spec)
 
+    def norm_tensors(self) -> tuple:
+        """Every BatchNorm layer's scale and shift (``spec_layout``'s names): decay class 1."""
+        return tuple(b.name + sfx for b in self.spec.bns() for sfx in (".weight", ".bias"))
+
     def _model_extra(self) -> dict:
         d = {}
         for name, (rm, rv) in self.running_stats().items():

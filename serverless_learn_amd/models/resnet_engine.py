@@ -82,6 +82,7 @@ class _Conv:
 class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
     tickets = ("ema_ticket",)  # (the update launches read opt_step; a cursor_bump advances it)
     opt_kernels = ("sl_adamw_flat", "sl_sgd_flat_lr")
+    group_kernels = ("sl_adamw_flat_groups", "sl_sgd_flat_lr_groups")
 
     def __init__(self, batch: int, device="cuda", lr: float = 0.05, momentum: float = 0.9,
                  weight_decay: float = 5e-4, seed: int = 0, world_size: int = 1, stem: str = "cifar",
@@ -495,7 +496,14 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             O.sgd_flat(self.params, self.grad, self.mom, self.lr, self.momentum, self.weight_decay,
                        shadow=self.shadow)
             return
-        if self.opt.adamw:
+        if self.opt.grouped:  # a weight decay per class (BatchNorm, fc.bias), read from the map
+            if self.opt.adamw:
+                O.adamw_flat_groups(self.params, self.grad, self.mom, self.v, self.opt_step, self.opt, self.decay_cls,
+                                    self.lr_tab, shadow=self.shadow)
+            else:
+                O.sgd_flat_lr_groups(self.params, self.grad, self.mom, self.opt_step, self.lr_tab, self.decay_cls,
+                                     self.opt.decays(), lr=self.lr, momentum=self.momentum, shadow=self.shadow)
+        elif self.opt.adamw:
             O.adamw_flat(self.params, self.grad, self.mom, self.v, self.opt_step, self.opt, self.lr_tab,
                          shadow=self.shadow)
         else:

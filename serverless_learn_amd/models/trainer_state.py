@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, OptSpec, check_accum_steps, clip_buffers,
-                         clip_grad_, ema_update_, require_kernels, sgd_update)
+                         clip_grad_, decay_vector, ema_update_, require_kernels, sgd_update, trainer_class_map)
 
 
 @dataclass
@@ -41,12 +41,19 @@ class TrainerState:
     owner's launches use (:attr:`tickets`).  This class is the weight EMA's definition on the
     trainers.
 
+    With decay groups on (``norm_weight_decay`` / ``bias_weight_decay``, ops/optim.py) also
+    ``decay_cls``, the class of every 64-element block of ``params`` (a uint8 tensor on
+    ``self.device``), and on the CPU ``decay_vec``, the float64 decay of every element that the
+    reference update takes.  Both follow from the model and the hyper-parameters: they are no
+    state, and a trainer without groups has neither attribute.
+
     The owner sets ``params`` (``n_params`` real entries, then any padding) before
     :meth:`_init_state`, and keeps ``cursor`` (an int, or a 1-element tensor on the device)."""
 
     device = torch.device("cpu")
     tickets = ()                  # of "opt_ticket" / "ema_ticket": the words the owner's launches use
     opt_kernels = ()              # entry points of the owner's step-counter rules
+    group_kernels = ()            # ... and of those rules with decay groups on
     accum_kernels = ACCUM_KERNELS  # ... and of its accumulated step
     graph = None                  # a captured step (GPU engines: a slot of utils/graphs.py)
     grad = None                   # the aggregated gradient of the last step, as the optimizer took it
@@ -69,7 +76,7 @@ class TrainerState:
         self.opt_step = self.opt_ticket = self.lr_tab = None
         if not spec.plain:
             if self._gpu:
-                require_kernels(spec, *self.opt_kernels)
+                require_kernels(spec, *(self.group_kernels if spec.grouped else self.opt_kernels))
             self.opt_step = word()
             self.opt_ticket = word() if "opt_ticket" in self.tickets else None
         self.clip_partials = self.clip_norm = self._grad_norm = None
@@ -81,7 +88,13 @@ class TrainerState:
             self.ema = self.params.clone()
             self.ema_step = word()
             self.ema_ticket = word() if "ema_ticket" in self.tickets else None
+        if spec.grouped:  # built once: the layout does not change
+            self.decay_cls = torch.from_numpy(trainer_class_map(self)).to(self.device)
         self._opt_tables()
+
+    def norm_tensors(self) -> tuple:
+        """Names (as in ``layout()``) of the normalisation layers' tensors: decay class 1."""
+        return ()
 
     @property
     def _gpu(self) -> bool:
@@ -94,6 +107,8 @@ class TrainerState:
         spec = self.opt
         if spec.emas:
             self.ema_tab = torch.from_numpy(spec.ema_table()).to(self.device)
+        if spec.grouped and not self._gpu:
+            self.decay_vec = decay_vector(self.decay_cls.numpy(), self.params.numel(), spec.decays())
         if not self._gpu:
             return
         if not spec.plain:
@@ -110,7 +125,8 @@ class TrainerState:
         if self.opt_step is None:
             sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
         else:
-            self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]))
+            self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]),
+                            self.decay_vec if self.opt.grouped else None)
             self.opt_step += 1
         if self.ema is not None:  # once per update, on the parameters just written
             t = min(int(self.ema_step[0]), self.ema_tab.numel() - 1)

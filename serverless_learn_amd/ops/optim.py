@@ -15,6 +15,11 @@ Either rule may be preceded by global-norm gradient clipping (``clip_grad_norm``
 Gradient accumulation (``accum_steps`` micro-batches per update) sums the micro-gradients ahead of
 all that with :func:`accum_flat`, one fp32 add per element in a fixed order.
 
+Weight decay may differ by parameter class (``norm_weight_decay``, ``bias_weight_decay``:
+torchvision's ``set_weight_decay``): :func:`decay_class_map` gives every 64-element block of a
+trainer's flat vector its class, :func:`decay_vector` the per-element decay the reference rules
+take, and the ``*_groups`` launches read the same map on the device.
+
 A weight EMA (``ema_decay``) follows every update: :func:`ema_update_` is its reference,
 :func:`ema_table` the per-step coefficients and :func:`ema_flat` the one launch that applies them and
 advances its own device-resident counter.
@@ -61,7 +66,10 @@ def lr_at(step: int, lr: float, schedule: str = "constant", warmup_steps: int = 
 
 
 def sgd_update(flat, mom, grad, lr, momentum, weight_decay):
-    """torch.optim.SGD semantics (dampening 0, no nesterov), in place."""
+    """torch.optim.SGD semantics (dampening 0, no nesterov), in place.  ``weight_decay``: a scalar
+    or one value per element (:func:`decay_vector`), taken in ``flat``'s precision as a scalar is."""
+    if torch.is_tensor(weight_decay):
+        weight_decay = weight_decay.to(flat.dtype)
     d = grad + weight_decay * flat
     if mom is not None:
         mom.mul_(momentum).add_(d)
@@ -70,12 +78,72 @@ def sgd_update(flat, mom, grad, lr, momentum, weight_decay):
 
 
 def adamw_update(flat, m, v, grad, lr_t, beta1, beta2, eps, weight_decay, t):
-    """torch.optim.AdamW semantics (no amsgrad), in place; ``t`` = step + 1."""
-    flat.mul_(1.0 - lr_t * weight_decay)
+    """torch.optim.AdamW semantics (no amsgrad), in place; ``t`` = step + 1.  ``weight_decay``: a
+    scalar or one float64 value per element (:func:`decay_vector`); either way ``1 - lr_t wd`` is
+    formed in float64 and rounded once to ``flat``'s precision."""
+    keep = 1.0 - lr_t * weight_decay
+    flat.mul_(keep.to(flat.dtype) if torch.is_tensor(keep) else keep)
     m.mul_(beta1).add_(grad, alpha=1.0 - beta1)
     v.mul_(beta2).addcmul_(grad, grad, value=1.0 - beta2)
     denom = v.sqrt().div_(math.sqrt(1.0 - beta2 ** t)).add_(eps)
     flat.addcdiv_(m, denom, value=-lr_t / (1.0 - beta1 ** t))
+
+
+# ---- per-class weight decay ----
+# Every element of a flat parameter vector has one of three classes; a class is constant over a
+# DECAY_BLOCK-element block, because every tensor of the vectors starts on such a boundary.
+DECAY_CLASSES = ("weight", "norm", "bias")
+CLS_WEIGHT, CLS_NORM, CLS_BIAS = 0, 1, 2
+DECAY_BLOCK = 64
+
+
+def check_group_decay(name: str, v) -> float | None:
+    """``norm_weight_decay`` / ``bias_weight_decay``: None (follow ``weight_decay``) or a finite
+    float >= 0."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"{name} must be None (follow weight_decay) or a finite number >= 0, got {v!r}")
+    return float(v)
+
+
+def decay_class_map(layout, n: int, norm=()) -> np.ndarray:
+    """The class of every :data:`DECAY_BLOCK`-element block of a flat vector of ``n`` elements, as
+    uint8: ``layout`` is a trainer's ``layout()`` (``[name, shape, offset]`` per tensor) and
+    ``norm`` the names of its normalisation layers' tensors (scale and shift: class 1).  Any other
+    tensor named ``*.bias`` is class 2 and the rest class 0.  Alignment padding takes the class of
+    the tensor it follows.  Every tensor must start on a block boundary."""
+    norm = set(norm)
+    cls = np.zeros((int(n) + DECAY_BLOCK - 1) // DECAY_BLOCK, dtype=np.uint8)
+    entries = sorted(layout, key=lambda e: e[2])
+    assert entries and entries[0][2] == 0, "the first tensor starts the vector"
+    for i, (name, shape, off) in enumerate(entries):
+        assert off % DECAY_BLOCK == 0, f"{name} starts at {off}: not on a {DECAY_BLOCK}-element boundary"
+        end = entries[i + 1][2] if i + 1 < len(entries) else int(n)
+        assert off + math.prod(shape) <= end, f"{name} overlaps the tensor after it"
+        c = CLS_NORM if name in norm else CLS_BIAS if name.endswith(".bias") else CLS_WEIGHT
+        cls[off // DECAY_BLOCK:(end + DECAY_BLOCK - 1) // DECAY_BLOCK] = c
+    assert not norm - {e[0] for e in entries}, "a normalisation tensor that is not in the layout"
+    return cls
+
+
+def trainer_class_map(trainer) -> np.ndarray:
+    """:func:`decay_class_map` of a trainer: its ``layout()``, its ``norm_tensors()`` (the ResNets'
+    BatchNorm scales and shifts; the MLP has none) and the length of its ``params``."""
+    return decay_class_map(trainer.layout(), int(trainer.params.numel()), trainer.norm_tensors())
+
+
+def decay_class_counts(cls: np.ndarray, n: int) -> tuple:
+    """Elements of the first ``n`` in each class (padding counted with its tensor)."""
+    per = np.repeat(np.asarray(cls), DECAY_BLOCK)[:int(n)]
+    return tuple(int((per == c).sum()) for c in range(len(DECAY_CLASSES)))
+
+
+def decay_vector(cls, n: int, decays, device="cpu") -> torch.Tensor:
+    """The float64 weight decay of each of ``n`` elements: ``decays[class]``."""
+    per = torch.as_tensor(np.asarray(cls)).long().repeat_interleave(DECAY_BLOCK)[:int(n)]
+    assert per.numel() == int(n), "the class map is shorter than the vector"
+    return torch.tensor([float(d) for d in decays], dtype=torch.float64)[per].to(device)
 
 
 CLIP_EPS = 1e-6  # torch.nn.utils.clip_grad_norm_'s constant
@@ -166,8 +234,14 @@ class OptSpec:
     clip_grad_norm: float = 0.0  # max global L2 norm of the gradient (0: off; inf: measure only)
     ema_decay: float = 0.0       # weight EMA after every update (0: off); no rule or kernel choice depends on it
     ema_warmup: bool = True      # decay_t = min(ema_decay, (1 + t) / (10 + t))
+    # the decay of BatchNorm scales and shifts / of the other biases (None: weight_decay); setting
+    # either switches the decay groups on, even to weight_decay's own value
+    norm_weight_decay: float | None = None
+    bias_weight_decay: float | None = None
 
     def __post_init__(self):
+        check_group_decay("norm_weight_decay", self.norm_weight_decay)
+        check_group_decay("bias_weight_decay", self.bias_weight_decay)
         if self.optimizer not in OPTIMIZERS:
             raise ValueError(f"unknown optimizer {self.optimizer!r} (choose from {OPTIMIZERS})")
         if self.lr_schedule not in SCHEDULES:
@@ -204,13 +278,27 @@ class OptSpec:
         return self.lr_schedule != "constant" or self.lr_warmup_steps > 0
 
     @property
+    def grouped(self) -> bool:
+        """Decay groups on: at least one of the two class decays is set."""
+        return self.norm_weight_decay is not None or self.bias_weight_decay is not None
+
+    def decays(self) -> tuple:
+        """The effective decay of each class (:data:`DECAY_CLASSES`)."""
+        wd = self.weight_decay
+        return (wd, wd if self.norm_weight_decay is None else self.norm_weight_decay,
+                wd if self.bias_weight_decay is None else self.bias_weight_decay)
+
+    @property
     def plain(self) -> bool:
-        """Momentum SGD at a fixed lr: the rule without a step counter."""
-        return not self.adamw and not self.scheduled
+        """Momentum SGD at a fixed lr without decay groups: the rule without a step counter.  A
+        grouped trainer always runs a step-counter rule (a grouped SGD trainer at a fixed lr runs
+        ``RULE_SGD_LR`` with no table, which reads the scalar lr), so it has an ``opt_step``, and
+        the plain rule's kernels and launches are what they were before groups existed."""
+        return not self.adamw and not self.scheduled and not self.grouped
 
     @property
     def rule(self) -> int:
-        return RULE_ADAMW if self.adamw else RULE_SGD_LR if self.scheduled else RULE_SGD
+        return RULE_ADAMW if self.adamw else RULE_SGD if self.plain else RULE_SGD_LR
 
     def lr_at(self, step: int) -> float:
         return lr_at(step, self.lr, self.lr_schedule, self.lr_warmup_steps, self.lr_decay_steps, self.lr_min_ratio)
@@ -233,13 +321,15 @@ class OptSpec:
         return (self.beta1, self.beta2, 1.0 - self.beta1, 1.0 - self.beta2, math.log(self.beta1),
                 math.log(self.beta2), self.adam_eps)
 
-    def update(self, flat, mom, v, grad, step: int) -> None:
-        """One reference update of 0-based ``step``, in place (the CPU trainers' optimizer)."""
+    def update(self, flat, mom, v, grad, step: int, decay=None) -> None:
+        """One reference update of 0-based ``step``, in place (the CPU trainers' optimizer).
+        ``decay``: the per-element weight decay of a grouped spec (:func:`decay_vector`)."""
+        assert (decay is not None) == self.grouped, "a grouped spec updates with its decay vector"
+        wd = self.weight_decay if decay is None else decay
         if self.adamw:
-            adamw_update(flat, mom, v, grad, self.lr_at(step), self.beta1, self.beta2, self.adam_eps,
-                         self.weight_decay, step + 1)
+            adamw_update(flat, mom, v, grad, self.lr_at(step), self.beta1, self.beta2, self.adam_eps, wd, step + 1)
         else:
-            sgd_update(flat, mom, grad, self.lr_at(step), self.momentum, self.weight_decay)
+            sgd_update(flat, mom, grad, self.lr_at(step), self.momentum, wd)
 
     def meta(self) -> dict:
         """Checkpoint metadata (``meta["optimizer"]``)."""
@@ -252,6 +342,10 @@ class OptSpec:
             d["clip_grad_norm"] = self.clip_grad_norm
         if self.emas:
             d.update(ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup))
+        if self.norm_weight_decay is not None:
+            d["norm_weight_decay"] = self.norm_weight_decay
+        if self.bias_weight_decay is not None:
+            d["bias_weight_decay"] = self.bias_weight_decay
         return d
 
 
@@ -263,8 +357,8 @@ def require_kernels(spec: OptSpec, *names: str) -> None:
     missing = [n for n in names if not hasattr(lib, n)]
     if missing:
         raise RuntimeError(f"optimizer {spec.optimizer!r} / lr_schedule {spec.lr_schedule!r} / clip_grad_norm "
-                           f"{spec.clip_grad_norm!r} / accum_steps > 1 / ema_decay {spec.ema_decay!r} need "
-                           f"{', '.join(missing)}: not in this kernel library")
+                           f"{spec.clip_grad_norm!r} / accum_steps > 1 / ema_decay {spec.ema_decay!r} / decay groups "
+                           f"{'on' if spec.grouped else 'off'} need {', '.join(missing)}: not in this kernel library")
 
 
 # ---- flat kernels ----
@@ -301,6 +395,41 @@ def adamw_flat(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     N.call("sl_adamw_flat", N.ptr(w), N.ptr(g), N.ptr(m), N.ptr(v), N.ptr(shadow), w.numel(), N.ptr(step),
            N.ptr(lr_tab), lr_tab.numel() if lr_tab is not None else 0, float(spec.lr), float(spec.weight_decay),
            float(grad_scale), *spec.adam_scalars(), N.stream_ptr())
+
+
+FLAT_GROUP_KERNELS = ("sl_adamw_flat_groups", "sl_sgd_flat_lr_groups")
+
+
+def _check_cls(cls: torch.Tensor, n: int) -> None:
+    assert cls.is_cuda and cls.dtype == torch.uint8 and cls.is_contiguous()
+    assert cls.numel() * DECAY_BLOCK >= n, "the class map is shorter than the vector"
+
+
+def sgd_flat_lr_groups(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor | None, step: torch.Tensor,
+                       lr_tab: torch.Tensor | None, cls: torch.Tensor, decays, lr: float = 0.0, momentum: float = 0.0,
+                       shadow: torch.Tensor | None = None, grad_scale: float = 1.0) -> None:
+    """:func:`sgd_flat_lr` with the weight decay ``decays[cls[i // 64]]`` for element ``i`` (``cls``:
+    uint8 on the device, :func:`decay_class_map`); without a table the learning rate is ``lr``."""
+    _check_flat(w, g, shadow)
+    _check_cls(cls, w.numel())
+    assert step.dtype == torch.int32 and (lr_tab is None or lr_tab.dtype == torch.float32)
+    wd, wd_norm, wd_bias = (float(d) for d in decays)
+    N.call("sl_sgd_flat_lr_groups", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), N.ptr(step),
+           N.ptr(lr_tab), lr_tab.numel() if lr_tab is not None else 0, float(lr), float(momentum), wd,
+           float(grad_scale), N.ptr(cls), wd_norm, wd_bias, N.stream_ptr())
+
+
+def adamw_flat_groups(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor,
+                      spec: OptSpec, cls: torch.Tensor, lr_tab: torch.Tensor | None = None,
+                      shadow: torch.Tensor | None = None, grad_scale: float = 1.0) -> None:
+    """:func:`adamw_flat` with the weight decay ``spec.decays()[cls[i // 64]]`` for element ``i``."""
+    _check_flat(w, g, shadow)
+    _check_cls(cls, w.numel())
+    assert step.dtype == torch.int32 and m.numel() == w.numel() and v.numel() == w.numel()
+    wd, wd_norm, wd_bias = (float(d) for d in spec.decays())
+    N.call("sl_adamw_flat_groups", N.ptr(w), N.ptr(g), N.ptr(m), N.ptr(v), N.ptr(shadow), w.numel(), N.ptr(step),
+           N.ptr(lr_tab), lr_tab.numel() if lr_tab is not None else 0, float(spec.lr), wd, float(grad_scale),
+           *spec.adam_scalars(), N.ptr(cls), wd_norm, wd_bias, N.stream_ptr())
 
 
 def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:

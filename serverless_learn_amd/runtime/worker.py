@@ -172,7 +172,15 @@ class Worker:
             kw.update(ema_decay=c.ema_decay, ema_warmup=c.ema_warmup)
         if c.n_classes != 10:  # (Config refuses anything but ten for the MLP)
             kw.update(classes=c.n_classes)
+        kw.update(c.decay_groups)  # norm_weight_decay / bias_weight_decay, where set
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
+        if c.decay_groups:
+            from ..ops.optim import DECAY_CLASSES, decay_class_counts
+
+            t = self.trainer
+            counts = decay_class_counts(t.decay_cls.cpu().numpy(), t.n_params)
+            self.log.info("decay_groups", **{f"{k}_decay": d for k, d in zip(DECAY_CLASSES, t.opt.decays())},
+                          **{f"{k}_elements": n for k, n in zip(DECAY_CLASSES, counts)})
         if c.ema_decay != 0:
             self.log.info("ema", decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
         if self.cfg.sync in ("gossip", "ps"):
