@@ -176,6 +176,15 @@ int sl_gossip_topk(const float* m, float* o, long n, long k, uint32_t* index_out
 int sl_gossip_scatter(float* m, float* o, const uint32_t* index, const float* value, long count, long n, double a,
                       int sign_o_only, hipStream_t stream);
 
+// groupnorm.hip: per-sample fused GroupNorm of the ResNet trainers (norm="group")
+int sl_gn_fwd(const uint16_t* x, const float* gamma, const float* beta, const uint16_t* res, uint16_t* y,
+              uint8_t* mask_out, float* mean, float* rstd, int N, int HW, int C, int G, int relu, float eps,
+              hipStream_t stream);
+int sl_gn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const float* rstd, const float* gamma,
+              const float* beta, const uint8_t* ymask, int mask_mode, uint16_t* dz_out, uint16_t* dx, float* ws,
+              int N, int HW, int C, int G, float eps, hipStream_t stream);
+int sl_gn_param_fold(const float* ws, int N, int C, float* grad_gamma, float* grad_beta, hipStream_t stream);
+
 // mlp_fused.hip
 long sl_mlp_x_tile_bytes(long rows);
 int sl_mlp_x_tile(const uint8_t* src, uint8_t* dst, long rows, hipStream_t stream);

@@ -41,6 +41,9 @@ KERNELS_SO = os.path.join(NATIVE_DIR, "libslkernels.so")
 # the same kernels built with -DSL_DETERMINISTIC=1 (fixed-point cross-workgroup sums, no
 # split-K atomics): loaded instead when the SL_DETERMINISTIC environment variable is 1
 KERNELS_DET_SO = os.path.join(NATIVE_DIR, "libslkernels_det.so")
+# per-file compiler flags on top of the common ones.  groupnorm.hip: scalar fp32 arithmetic only
+# (no packed v_pk_* forms), so its fixed-order sums round the same way in every instantiation
+FILE_FLAGS = {"groupnorm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _core_so_name() -> str:
@@ -92,7 +95,8 @@ def build_kernels(force: bool = False, jobs: int = 8, deterministic: bool = Fals
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
-            procs.append((src, subprocess.Popen([hipcc, *flags, "-c", src, "-o", obj],
+            extra = FILE_FLAGS.get(os.path.basename(src), [])
+            procs.append((src, subprocess.Popen([hipcc, *flags, *extra, "-c", src, "-o", obj],
                                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         while len([p for _, p in procs if p.poll() is None]) >= jobs:
             procs[0][1].wait()

@@ -58,6 +58,9 @@ class Config:
     model: str = "mlp"                 # mlp | resnet18 | simulate (reference: vector += 1)
     classes: int = 0                   # resnet18: outputs of the classifier head (1..256); 0 = the dataset's own
                                        # count, 10 or synthetic-cifar100's 100.  mlp / simulate: 0 or 10
+    norm: str = "batch"                # resnet18: batch (BatchNorm) | group (GroupNorm: no running statistics, the
+                                       # flat vector is the whole model; cifar stem, inputs up to 32 x 32)
+    norm_groups: int = 32              # norm=group: groups per layer, one of 8, 16, 32, 64
     batch: int = 1024
     lr: float = 0.05
     momentum: float = 0.9
@@ -124,6 +127,7 @@ class Config:
         self._validate_eval()
         self._validate_classes()
         self._validate_decay_groups()
+        self._validate_norm()
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
         if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:
@@ -174,6 +178,16 @@ class Config:
                 raise ValueError(f"{name}: the simulate model has no optimizer")
         if self.norm_weight_decay != -1 and self.model == "mlp":
             raise ValueError("norm_weight_decay: the mlp model has no normalisation layer (model='resnet18')")
+
+    def _validate_norm(self) -> None:
+        if self.norm not in ("batch", "group"):
+            raise ValueError(f"norm must be 'batch' or 'group', got {self.norm!r}")
+        if self.norm == "batch":
+            return
+        if self.model in ("mlp", "simulate"):
+            raise ValueError(f"norm={self.norm!r}: the {self.model} model has no normalisation layer (model='resnet18')")
+        if isinstance(self.norm_groups, bool) or self.norm_groups not in (8, 16, 32, 64):
+            raise ValueError(f"norm_groups must be one of 8, 16, 32, 64, got {self.norm_groups!r}")
 
     @property
     def decay_groups(self) -> dict:

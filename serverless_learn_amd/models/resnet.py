@@ -34,6 +34,25 @@ ALIGN = 64
 CIFAR_MEAN = (0.4914, 0.4822, 0.4465)
 CIFAR_STD = (0.2470, 0.2435, 0.2616)
 STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))
+NORMS = ("batch", "group")
+NORM_GROUPS = (8, 16, 32, 64)  # with 64..512 channels: 1..64 channels per group
+
+
+def check_norm(norm: str, groups, stem: str, in_hw: int) -> int:
+    """The trainers' ``norm=`` / ``norm_groups=``: refuses an unknown kind and, under ``"group"``,
+    a group count outside :data:`NORM_GROUPS` and the shapes whose per-sample 64-channel slabs do
+    not fit on chip (the imagenet stem, inputs above 32 x 32: csrc/kernels/groupnorm.hip).  Returns
+    the group count (0 under ``"batch"``)."""
+    if norm not in NORMS:
+        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+    if norm == "batch":
+        return 0
+    if isinstance(groups, bool) or groups not in NORM_GROUPS:
+        raise ValueError(f"norm_groups must be one of {NORM_GROUPS}, got {groups!r}")
+    if stem == "imagenet" or in_hw > 32:
+        raise ValueError(f"norm='group' serves the cifar stem up to 32 x 32 inputs (a sample's 64-channel slab "
+                         f"is kept on chip), got stem={stem!r}, in_hw={in_hw}")
+    return int(groups)
 
 
 @dataclass
@@ -210,9 +229,14 @@ def normalize_input(x_u8: torch.Tensor) -> torch.Tensor:
 
 
 def ref_forward(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, training: bool = True,
-                running: dict | None = None, momentum: float = 0.1, eps: float = 1e-5) -> torch.Tensor:
-    """fp32 NCHW torch forward of exactly the network the HIP engine runs."""
+                running: dict | None = None, momentum: float = 0.1, eps: float = 1e-5, norm: str = "batch",
+                groups: int = 32) -> torch.Tensor:
+    """fp32 NCHW torch forward of exactly the network the HIP engine runs.  ``norm="group"``: every
+    normalisation is ``F.group_norm`` over ``groups`` groups (no running statistics, and
+    ``training`` makes no difference)."""
     def bn(x, b: BNSpec):
+        if norm == "group":
+            return F.group_norm(x, groups, flat[b.g_off:b.g_off + b.c], flat[b.b_off:b.b_off + b.c], eps)
         rm, rv = running[b.name] if running is not None else (None, None)
         return F.batch_norm(x, rm, rv, flat[b.g_off:b.g_off + b.c], flat[b.b_off:b.b_off + b.c],
                             training=training or rm is None, momentum=momentum, eps=eps)
@@ -235,12 +259,14 @@ def ref_forward(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, traini
 
 
 def ref_grads(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, y: torch.Tensor, grad_scale: float,
-              running: dict | None = None, targets: torch.Tensor | None = None):
+              running: dict | None = None, targets: torch.Tensor | None = None, norm: str = "batch",
+              groups: int = 32):
     """(loss_sum, correct, grad_flat) with d(loss_i)/dlogits scaled by grad_scale.  ``x_u8`` is in
     pixel units (u8, or float after a mix); ``targets`` ([B, classes] probabilities) replaces the
-    one-hot ``y`` in the loss, and ``correct`` stays the argmax against ``y``."""
+    one-hot ``y`` in the loss, and ``correct`` stays the argmax against ``y``.  ``norm`` / ``groups``
+    as in :func:`ref_forward`."""
     w = flat.detach().clone().float().requires_grad_(True)
-    logits = ref_forward(spec, w, x_u8, True, running)
+    logits = ref_forward(spec, w, x_u8, True, running, norm=norm, groups=groups)
     losses = F.cross_entropy(logits, y.long() if targets is None else targets.to(logits.dtype), reduction="none")
     (losses.sum() * grad_scale).backward()
     correct = (logits.argmax(1) == y.long()).float().sum()
@@ -251,7 +277,16 @@ class ResNetModel:
     """What the two ResNet trainers add to the shared state (``self.spec``: the ResNetSpec): the
     model's description, and the BatchNorm running statistics (``running_stats()``: name -> (mean,
     var)) in the checkpoint and among ``buffers()``, ahead of the optimizer's.  The statistics are
-    not averaged by the weight EMA: they already are a moving average."""
+    not averaged by the weight EMA: they already are a moving average.
+
+    With ``norm = "group"`` (``norm_groups`` groups) a ``BNSpec``'s scale and shift are a
+    GroupNorm's, at the same offsets: there are no running statistics (``running_stats()`` is
+    empty), so the flat vector is the whole model.  The flat size is the same under both kinds, so
+    a checkpoint of one loads into a trainer of the other without a size error; ``model_name``
+    (in the checkpoint's metadata) tells them apart."""
+
+    norm = "batch"
+    norm_groups = 0
 
     @property
     def n_params(self) -> int:
@@ -259,7 +294,8 @@ class ResNetModel:
 
     @property
     def model_name(self) -> str:
-        return f"resnet18-{self.spec.stem}"
+        gn = f"-gn{self.norm_groups}" if self.norm == "group" else ""
+        return f"resnet18-{self.spec.stem}{gn}"
 
     def layout(self):
         return spec_layout(self.spec)
@@ -296,12 +332,14 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
                  seed: int = 0, world_size: int = 1, stem: str = "cifar", classes: int = 10,
                  flat: torch.Tensor | None = None, in_hw: int | None = None, augment: str = "none",
                  augment_pad: int = 4, shuffle: bool = False, label_smoothing: float = 0.0, mixup_alpha: float = 0.0,
-                 cutmix_alpha: float = 0.0, accum_steps: int = 1, **opt):
+                 cutmix_alpha: float = 0.0, accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32,
+                 **opt):
         from ..data import augment as A
 
         if isinstance(classes, bool) or int(classes) != classes or not 1 <= classes <= 256:
             raise ValueError(f"classes must be an integer in 1..256 (the u8 label), got {classes!r}")
         self.spec = resnet18_spec(stem, int(classes), in_hw)
+        self.norm, self.norm_groups = norm, check_norm(norm, norm_groups, stem, self.spec.in_hw)
         A.check(augment, augment_pad, self.spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         # the training input pipeline (data/augment.py), keyed on (seed, cursor, sample) like the
@@ -315,7 +353,8 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         self.last_mix = None
         self._init_cpu(flat if flat is not None else init_params(self.spec, seed), batch, lr, momentum,
                        weight_decay, world_size, accum_steps, opt)
-        self.running = running_stats(self.spec)
+        self.running = running_stats(self.spec) if norm == "batch" else {}
+        self._norm_kw = dict(norm=norm, groups=self.norm_groups) if norm == "group" else {}
 
     def running_stats(self) -> dict:
         return self.running
@@ -350,14 +389,14 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         if mixes or self.label_smoothing > 0:
             targets = torch.from_numpy(A.soft_targets(ys.cpu().numpy(), self.last_mix, self.label_smoothing,
                                                       self.spec.classes))
-        return ref_grads(self.spec, self.params, xs, ys, self.grad_scale, self.running, targets)
+        return ref_grads(self.spec, self.params, xs, ys, self.grad_scale, self.running, targets, **self._norm_kw)
 
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False):
         """Inference with the BatchNorm running statistics (eval mode); ``ema=True``: of the averaged
         parameters, with the same running statistics (those are not averaged)."""
         with torch.no_grad():
             logits = ref_forward(self.spec, self._eval_weights(ema), x_u8.reshape(-1, self.spec.in_hw, self.spec.in_hw, 3),
-                                 False, self.running)
+                                 False, self.running, **self._norm_kw)
             y = y_u8.reshape(-1).long()
             loss = F.cross_entropy(logits, y, reduction="mean")
             acc = (logits.argmax(1) == y).float().mean()
@@ -378,7 +417,7 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         with torch.no_grad():
             for s in range(0, n, 1024):  # (running statistics: the rows are independent, and reports add)
                 ys = y[s:s + 1024]
-                logits = ref_forward(self.spec, w, x[s:s + 1024], False, self.running)
+                logits = ref_forward(self.spec, w, x[s:s + 1024], False, self.running, **self._norm_kw)
                 rows = F.cross_entropy(logits, torch.where(ys < ncls, ys, 0), reduction="none").float()
                 part = eval_reference(logits, ys, rows, ncls, topk, wide=ncls > 16)
                 rep = part if rep is None else rep + part

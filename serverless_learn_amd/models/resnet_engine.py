@@ -32,6 +32,13 @@ Per step:
             momentum, weight decay, bf16 shadow) + one launch that re-lays the
             bf16 conv weights out for dgrad; with ema_decay= on, one launch
             between them that moves the weight EMA towards the new parameters.
+
+With ``norm="group"`` the normalisation layers are GroupNorms run by the per-sample kernels of
+csrc/kernels/groupnorm.hip, through a forward and backward of their own (``_forward_gn`` /
+``_backward_gn``): plain convolutions, one ``gn_fwd`` per layer (statistics, normalisation, residual,
+ReLU and mask in one pass) and one ``gn_bwd`` + ``gn_param_fold`` per layer.  There is no statistics
+arena and there are no running statistics, evaluation runs the training forward, and none of the
+BatchNorm fusions above apply; input pipeline, loss, buckets, update, EMA and capture are shared.
 """
 from __future__ import annotations
 
@@ -40,7 +47,8 @@ import os
 import torch
 
 from ..utils.graphs import GraphedStep
-from .resnet import CIFAR_MEAN, CIFAR_STD, BlockSpec, BNSpec, ConvSpec, ResNetModel, init_params, resnet18_spec
+from .resnet import (CIFAR_MEAN, CIFAR_STD, BlockSpec, BNSpec, ConvSpec, ResNetModel, check_norm, init_params,
+                     resnet18_spec)
 from .trainer_state import StepStats, TrainerState
 
 LOGIT_LD = 16  # dlogits row stride up to 16 classes (classes padded for 16-B gathers); above: ops.cnn.logit_ld
@@ -70,6 +78,21 @@ class _BN:
         self.run_var = torch.ones(c, device=dev)
 
 
+class _GN:
+    """Per-GroupNorm buffers (norm="group"): the scale / shift and their gradients in the flat
+    vectors, at the ``BNSpec``'s offsets, and each (sample, group)'s forward statistics."""
+
+    def __init__(self, spec: BNSpec, params, grad, batch, groups, dev):
+        c = spec.c
+        self.spec = spec
+        self.gamma = params[spec.g_off:spec.g_off + c]
+        self.beta = params[spec.b_off:spec.b_off + c]
+        self.ggamma = grad[spec.g_off:spec.g_off + c]
+        self.gbeta = grad[spec.b_off:spec.b_off + c]
+        self.mean = torch.zeros(batch, groups, device=dev)
+        self.rstd = torch.zeros(batch, groups, device=dev)
+
+
 class _Conv:
     def __init__(self, spec: ConvSpec, params, shadow, grad, dev, ld_out=None):
         self.spec = spec
@@ -89,7 +112,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
                  label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
-                 accum_steps: int = 1, **opt):
+                 accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32, **opt):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
@@ -101,6 +124,10 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.logit_ld = K.logit_ld(classes)
         self.wide = classes > K.NARROW_CLASSES
         self.spec = spec = resnet18_spec(stem, int(classes), in_hw)
+        # norm="group": every BNSpec is a GroupNorm of norm_groups groups, run by the per-sample
+        # kernels of csrc/kernels/groupnorm.hip through a forward / backward of their own
+        self.norm, self.norm_groups = norm, check_norm(norm, norm_groups, stem, spec.in_hw)
+        group = norm == "group"
         A.check(augment, augment_pad, spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         _native.lib()
@@ -127,7 +154,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self._init_state(batch, lr, momentum, weight_decay, world_size, accum_steps, opt)
         self.grad = torch.zeros_like(self.params)
         self.shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
-        bns = list(spec.bns())
+        bns = [] if group else list(spec.bns())  # (GroupNorm: no statistics arena, no running statistics)
         rsz = {b.name: (K.rsum_floats(2 * b.c) + 3) // 4 * 4 for b in bns}  # 16-B aligned regions
         self.arena = torch.zeros(sum(2 * rsz[b.name] for b in bns), device=dev)
         off = 0
@@ -135,6 +162,11 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         for b in bns:
             self.bn[b.name] = _BN(b, self.params, self.grad, self.arena, off, dev, rsz[b.name])
             off += 2 * rsz[b.name]
+        if group:
+            self.gn = {b.name: _GN(b, self.params, self.grad, batch, self.norm_groups, dev) for b in spec.bns()}
+            # gn_bwd's per-sample rows of dgamma / dbeta, [batch][2][C] of the widest layer: every
+            # backward launch is followed by its fold on the same stream
+            self.gn_ws = torch.empty(K.gn_ws_floats(batch, max(b.c for b in spec.bns())), device=dev)
         self.conv = {c.name: _Conv(c, self.params, self.shadow, self.grad, dev) for c in spec.convs()}
         self.fc_w = self.shadow[spec.fc_w:spec.fc_w + classes * 512]
         self.fc_b = self.params[spec.fc_b:spec.fc_b + classes]
@@ -186,11 +218,13 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             if blk.down is not None:
                 st["cs"] = torch.empty(shp, **bf)
                 st["dcs"] = torch.empty(shp, **bf)
+                if group:  # the shortcut's GroupNorm output, the residual of the block's last launch
+                    st["sc"] = torch.empty(shp, **bf)
                 if not self._shortcut_even(blk):  # else the shortcut gradient goes straight into dx
                     st["dxs"] = torch.empty_like(cur)
             st["dx"] = torch.empty_like(cur)
             c2s = blk.conv2
-            st["bnin"] = self.bn_onload and K.conv3x3_bnin_applicable(shp, c2s.cout, c2s.k, c2s.stride, c2s.pad)
+            st["bnin"] = not group and self.bn_onload and K.conv3x3_bnin_applicable(shp, c2s.cout, c2s.k, c2s.stride, c2s.pad)
             self.blocks.append(st)
             cur = st["y"]
         self.feat_in = cur
@@ -198,7 +232,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         # conv1 (forward, weight gradient) and its residual; both rebuild it from c0
         b0 = self.blocks[0]
         c1s = b0["spec"].conv1
-        self.stem_onload = (self.bn_onload and spec.stem != "imagenet" and b0["spec"].down is None
+        self.stem_onload = (not group and self.bn_onload and spec.stem != "imagenet" and b0["spec"].down is None
                             and K.conv3x3_bnin_applicable(self.c0.shape, c1s.cout, c1s.k, c1s.stride, c1s.pad))
         self.feat = torch.empty(B, 1, 1, 512, **bf)
         self.dfeat = torch.empty_like(self.feat)
@@ -228,7 +262,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         # split-K slab(s) of the weight gradients, grown on the first step
         self.wgws = K.WgradWorkspace(dev, alternate=self.wgrad_side is not None)
         # BN-backward sums in the data-gradient epilogues instead of bn_bwd_reduce passes
-        self.fuse_bn_bwd = os.environ.get("SL_BNB_FUSE", "1") != "0"
+        self.fuse_bn_bwd = not group and os.environ.get("SL_BNB_FUSE", "1") != "0"
 
         items = [(c.w, c.wt, c.spec.cout, c.spec.k * c.spec.k, c.spec.cin, c.ldt)
                  for c in self.conv.values() if c.spec.name != "stem"]
@@ -268,9 +302,9 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         c = conv.spec
         K.conv_fwd(x, conv.w, c.cout, c.k, c.stride, c.pad, y=out, stats=bn.stats_buf)
 
-    def forward(self, train: bool = True):
-        K, spec = self.K, self.spec
-        self.arena.zero_()
+    def _forward_input(self, train: bool) -> None:
+        """The batch at the cursor -> x0 / labels (the training input pipeline, or input_norm)."""
+        K = self.K
         if train and self.mixes:
             K.input_mix(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, self.aug_out, self.mix_out,
                         self.mix_tab, CIFAR_MEAN, CIFAR_STD, seed=self.seed, shuffle=self.shuffle,
@@ -282,6 +316,13 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                         pad=self.augment_pad)
         else:
             K.input_norm(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)
+
+    def forward(self, train: bool = True):
+        if self.norm == "group":
+            return self._forward_gn(train)
+        K, spec = self.K, self.spec
+        self.arena.zero_()
+        self._forward_input(train)
         sbn = self.bn[spec.stem_bn.name]
         self._conv_bn(self.x0, self.conv["stem"], sbn, self.c0)
         cnt0 = self.c0.numel() // 64
@@ -316,6 +357,11 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             else:
                 K.bn_apply_stats(st["c2"], b2, st["y"], cnt, res=st["x"], momentum=self.bn_momentum,
                                  mask_out=st["ym"])
+        self._forward_head(train)
+
+    def _forward_head(self, train: bool) -> None:
+        """Average pool, classifier and loss (``train``: with the bias gradient and soft targets)."""
+        K, spec = self.K, self.spec
         K.avgpool_fwd(self.feat_in, self.feat)
         K.conv_fwd(self.feat, self.fc_w, spec.classes, 1, 1, 0, yf=self.logits, bias=self.fc_b)
         if train and (self.mixes or self.label_smoothing > 0):
@@ -333,6 +379,8 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         """``hook=False``: no bucket hook is called (an accumulated step's earlier micro-batches).
         ``fold``: the partial sum ``acc`` of the earlier micro-batches is added into each bucket's
         range of ``grad`` just before the hook takes it (the last micro-batch)."""
+        if self.norm == "group":
+            return self._backward_gn(hook, fold)
         K, spec = self.K, self.spec
         handles = []
         pending_from = spec.n_flat  # grad[pending_from:] is final and not yet reduced
@@ -448,6 +496,98 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             K.wgrad_side_join(end=True)
         return handles
 
+    # ---- norm="group": per-sample fused GroupNorm (csrc/kernels/groupnorm.hip) ----
+    def _gn_fwd(self, x, name: str, y, relu=True, res=None, mask_out=None) -> None:
+        g = self.gn[name]
+        self.K.gn_fwd(x, g.gamma, g.beta, y, g.mean, g.rstd, self.norm_groups, relu=relu, res=res, mask_out=mask_out)
+
+    def _gn_bwd(self, dy, x, name: str, dx, **mask) -> None:
+        """One GroupNorm's backward and the fold of its dgamma / dbeta rows into the flat gradient."""
+        g = self.gn[name]
+        self.K.gn_bwd(dy, x, g.gamma, g.beta, g.mean, g.rstd, dx, self.gn_ws, self.norm_groups, **mask)
+        self.K.gn_param_fold(self.gn_ws, self.batch, g.ggamma, g.gbeta)
+
+    def _forward_gn(self, train: bool = True) -> None:
+        """Per block: c1 = conv(x), a1 = relu(gn1(c1)), c2 = conv(a1), y = relu(gn2(c2) + sc) with
+        sc = x or gnd(conv_down(x)) and y's 1-bit mask stored.  Plain convolutions (no statistics
+        epilogue), one launch per GroupNorm; the same function in training and evaluation."""
+        K, spec = self.K, self.spec
+        self._forward_input(train)
+        sc = spec.stem_conv
+        K.conv_fwd(self.x0, self.conv["stem"].w, sc.cout, sc.k, sc.stride, sc.pad, y=self.c0)
+        self._gn_fwd(self.c0, spec.stem_bn.name, self.a0)
+        for st in self.blocks:
+            blk: BlockSpec = st["spec"]
+            c1, c2, d = blk.conv1, blk.conv2, blk.down
+            K.conv_fwd(st["x"], self.conv[c1.name].w, c1.cout, c1.k, c1.stride, c1.pad, y=st["c1"])
+            self._gn_fwd(st["c1"], blk.bn1.name, st["a1"])
+            K.conv_fwd(st["a1"], self.conv[c2.name].w, c2.cout, c2.k, c2.stride, c2.pad, y=st["c2"])
+            res = st["x"]
+            if d is not None:
+                K.conv_fwd(st["x"], self.conv[d.name].w, d.cout, d.k, d.stride, d.pad, y=st["cs"])
+                self._gn_fwd(st["cs"], blk.dbn.name, st["sc"], relu=False)
+                res = st["sc"]
+            self._gn_fwd(st["c2"], blk.bn2.name, st["y"], res=res, mask_out=st["ym"])
+        self._forward_head(train)
+
+    def _backward_gn(self, hook: bool = True, fold: bool = False):
+        """The mirror of :meth:`_forward_gn`; bucket hooks fire at the offsets of :meth:`backward`."""
+        K, spec = self.K, self.spec
+        handles = []
+        pending_from = spec.n_flat
+        bucket_elems = self.bucket_bytes // 4
+        side = self.wgrad_side
+        if side is not None:
+            K.wgrad_side_begin(side)
+
+        def maybe_bucket(lo, force=False):
+            nonlocal pending_from
+            if self.bucket_hook is None or not hook:
+                return
+            if force or (pending_from - lo) >= bucket_elems:
+                if side is not None:
+                    K.wgrad_side_join(end=False)
+                if fold:
+                    self.O.accum_flat(self.grad[lo:pending_from], self.acc[lo:pending_from], True)
+                handles.append(self.bucket_hook(self.grad[lo:pending_from]))
+                pending_from = lo
+
+        K.conv_wgrad(self.feat, self.dlogits, spec.classes, 1, 1, 0, self.fc_gw, ws=self.wgws)
+        K.conv_dgrad(self.dlogits, self.fc_wt, 512, 1, 1, 0, self.dfeat)
+        K.avgpool_bwd(self.dfeat.view(self.batch, 512), self.dfeat_in)
+        dy = self.dfeat_in
+        for st in reversed(self.blocks):
+            blk: BlockSpec = st["spec"]
+            c1, c2 = self.conv[blk.conv1.name], self.conv[blk.conv2.name]
+            # y = relu(gn2(c2) + sc): dz = dy * 1[y > 0] feeds gn2 and the shortcut
+            self._gn_bwd(dy, st["c2"], blk.bn2.name, st["dc2"], y_mask=st["ym"], dz_out=st["dz"])
+            dx, add, add_even = st["dx"], st["dz"], False
+            if blk.down is not None:
+                cd = self.conv[blk.down.name]
+                self._gn_bwd(st["dz"], st["cs"], blk.dbn.name, st["dcs"])
+                K.conv_wgrad(st["x"], st["dcs"], blk.down.cout, 1, blk.down.stride, 0, cd.g, ws=self.wgws)
+                if self._shortcut_even(blk):
+                    K.conv_dgrad_s2_even(st["dcs"], cd.wt, blk.down.cin, dx)
+                    add, add_even = dx, True
+                else:
+                    K.conv_dgrad(st["dcs"], cd.wt, blk.down.cin, 1, blk.down.stride, 0, st["dxs"])
+                    add = st["dxs"]
+            K.conv_wgrad(st["a1"], st["dc2"], blk.conv2.cout, 3, 1, 1, c2.g, ws=self.wgws)
+            K.conv_dgrad(st["dc2"], c2.wt, blk.conv2.cin, 3, 1, 1, st["da1"])
+            # a1 = relu(gn1(c1)): the mask is the sign of the recomputed gn1(c1)
+            self._gn_bwd(st["da1"], st["c1"], blk.bn1.name, st["dc1"], recompute_mask=True)
+            K.conv_wgrad(st["x"], st["dc1"], blk.conv1.cout, 3, blk.conv1.stride, 1, c1.g, ws=self.wgws)
+            K.conv_dgrad(st["dc1"], c1.wt, blk.conv1.cin, 3, blk.conv1.stride, 1, dx, add=add, add_even=add_even)
+            dy = dx
+            maybe_bucket(blk.conv1.off)
+        self._gn_bwd(dy, self.c0, spec.stem_bn.name, self.dc0, recompute_mask=True)
+        sc = spec.stem_conv
+        K.conv_wgrad(self.x0, self.dc0, 64, sc.k, sc.stride, sc.pad, self.conv["stem"].g, ws=self.wgws)
+        maybe_bucket(0, force=True)
+        if side is not None:
+            K.wgrad_side_join(end=True)
+        return handles
+
     def _accum_sums(self, i: int) -> None:
         """After micro-batch ``i`` of an accumulated step: its gradient, per-sample loss and correct
         into the partial sums (stored after the first, added after the others)."""
@@ -541,6 +681,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.refresh_shadows()
 
     def running_stats(self) -> dict:
+        """(Empty under norm="group": the checkpoint and ``buffers()`` then add nothing.)"""
         return {name: (b.run_mean, b.run_var) for name, b in self.bn.items()}
 
     # ---- inference with running statistics ----
@@ -552,7 +693,10 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         """Eval-mode forward of the current batch: every BatchNorm normalises with its running
         statistics (no batch statistics are computed, none are updated), then loss / correct
         / logits.  Same kernels as training -- conv_fwd without the statistics epilogue and
-        bn_apply with coefficients folded from (gamma, beta, running mean, running var)."""
+        bn_apply with coefficients folded from (gamma, beta, running mean, running var).
+        norm="group" has no eval mode: the training forward without the loss's gradients."""
+        if self.norm == "group":
+            return self._forward_gn(train=False)
         K, spec = self.K, self.spec
         co = {name: self._eval_coef(b) for name, b in self.bn.items()}
         K.input_norm(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)

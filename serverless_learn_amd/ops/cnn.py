@@ -434,6 +434,69 @@ def bn_bwd_apply_dual(dz, xa, sums_a, coef_a, gg_a, gb_a, dx_a, xb, sums_b, coef
            float(rows), N.stream_ptr())
 
 
+# ---- GroupNorm, fused per sample (csrc/kernels/groupnorm.hip) ----
+GN_SLAB = 64       # channels one workgroup owns: a group never straddles a slab
+GN_MAX_HW = 1024   # pixels of the largest slab kept on chip (128 KB)
+GN_GROUPS = (8, 16, 32, 64)  # what the trainers offer: with 64..512 channels, 1..64 channels per group
+
+
+def gn_supported(hw: int, c: int, groups: int) -> bool:
+    """Whether the per-sample kernels serve [*, hw, c] with ``groups`` groups (the launchers'
+    own test: they return non-zero and launch nothing otherwise)."""
+    if hw < 1 or hw > GN_MAX_HW or c < GN_SLAB or c % GN_SLAB or groups < 1 or c % groups:
+        return False
+    cpg = c // groups
+    return cpg <= GN_SLAB and cpg & (cpg - 1) == 0
+
+
+def _gn_dims(x, groups: int):
+    n, c = x.shape[0], x.shape[-1]
+    return n, x.numel() // (n * c), c, int(groups)
+
+
+def gn_fwd(x, gamma, beta, y, mean, rstd, groups: int, relu=True, res=None, mask_out=None, eps=1e-5):
+    """y = relu?(gn(x) (+ res)) of x [N, ..., C] bf16 in ``groups`` groups of contiguous channels;
+    ``mean`` / ``rstd`` (fp32 [N, groups]) receive each (sample, group)'s statistics for
+    :func:`gn_bwd`.  ``res``: x's shape, already final.  ``mask_out`` as in :func:`bn_apply_stats`."""
+    n, hw, c, g = _gn_dims(x, groups)
+    assert y.shape == x.shape and (res is None or res.shape == x.shape)
+    assert gamma.numel() == c and beta.numel() == c and mean.numel() == n * g and rstd.numel() == n * g
+    if mask_out is not None:
+        assert mask_out.dtype == torch.uint8 and mask_out.numel() * 8 == x.numel() and mask_out.is_contiguous()
+    N.call("sl_gn_fwd", _bf16(x), _f32(gamma), _f32(beta), _bf16(res) if res is not None else None, _bf16(y),
+           p(mask_out), _f32(mean), _f32(rstd), n, hw, c, g, 1 if relu else 0, float(eps), N.stream_ptr())
+
+
+def gn_ws_floats(n: int, c: int) -> int:
+    """Floats of :func:`gn_bwd`'s workspace for ``n`` samples of ``c`` channels ([n][2][c])."""
+    return 2 * int(n) * int(c)
+
+
+def gn_bwd(dy, x, gamma, beta, mean, rstd, dx, ws, groups: int, y_mask=None, recompute_mask=False, dz_out=None,
+           eps=1e-5):
+    """dx of ``y = relu?(gn(x) (+ res))`` and each sample's per-channel dgamma / dbeta into ``ws``
+    (fp32, :func:`gn_ws_floats`; :func:`gn_param_fold` adds them into the gradient).  The ReLU mask:
+    ``y_mask`` (the forward's ``mask_out``), ``recompute_mask`` (the sign of gn(x), for a plain
+    ``relu(gn(x))``, rebuilt with the forward's own fp64 statistics and ``eps``), or neither (no ReLU).  ``dz_out`` receives dz = dy * mask (the skip path's)."""
+    n, hw, c, g = _gn_dims(x, groups)
+    assert dy.shape == x.shape == dx.shape and (dz_out is None or dz_out.shape == x.shape)
+    assert y_mask is None or not recompute_mask
+    assert gamma.numel() == c and beta.numel() == c and mean.numel() == n * g and rstd.numel() == n * g
+    assert ws.dtype == torch.float32 and ws.numel() >= gn_ws_floats(n, c) and ws.is_contiguous()
+    if y_mask is not None:
+        assert y_mask.dtype == torch.uint8 and y_mask.numel() * 8 == x.numel() and y_mask.is_contiguous()
+    N.call("sl_gn_bwd", _bf16(dy), _bf16(x), _f32(mean), _f32(rstd), _f32(gamma), _f32(beta), p(y_mask),
+           1 if y_mask is not None else (2 if recompute_mask else 0), _bf16(dz_out) if dz_out is not None else None,
+           _bf16(dx), p(ws), n, hw, c, g, float(eps), N.stream_ptr())
+
+
+def gn_param_fold(ws, n: int, grad_gamma, grad_beta):
+    """grad_gamma / grad_beta += the ``n`` samples' rows of :func:`gn_bwd`'s ``ws``, in sample order."""
+    c = grad_gamma.numel()
+    assert grad_beta.numel() == c and ws.dtype == torch.float32 and ws.numel() >= gn_ws_floats(n, c)
+    N.call("sl_gn_param_fold", p(ws), int(n), c, _f32(grad_gamma), _f32(grad_beta), N.stream_ptr())
+
+
 def maxpool_fwd(x, y, arg, k=3, s=2, pad=1):
     n, h, w, c = x.shape
     _, oh, ow, _ = y.shape

@@ -173,7 +173,11 @@ class Worker:
         if c.n_classes != 10:  # (Config refuses anything but ten for the MLP)
             kw.update(classes=c.n_classes)
         kw.update(c.decay_groups)  # norm_weight_decay / bias_weight_decay, where set
+        if c.norm != "batch":  # (a stem or input size it does not serve is refused by the trainer)
+            kw.update(norm=c.norm, norm_groups=c.norm_groups)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
+        if c.norm != "batch":
+            self.log.info("norm", kind=c.norm, groups=int(c.norm_groups))
         if c.decay_groups:
             from ..ops.optim import DECAY_CLASSES, decay_class_counts
 
