@@ -185,6 +185,16 @@ int sl_gn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const fl
               int N, int HW, int C, int G, float eps, hipStream_t stream);
 int sl_gn_param_fold(const float* ws, int N, int C, float* grad_gamma, float* grad_beta, hipStream_t stream);
 
+// lars.hip: layer-wise trust ratios over the ResNet trainers' flat vector (optimizer="lars")
+int sl_lars_chunk();
+int sl_lars_norms(const float* w, const float* g, const int* chunks, int n_chunks, double* partials,
+                  hipStream_t stream);
+int sl_lars_trust(const double* partials, const int* tensors, int T, double eta, double eps, double wd, float* out,
+                  hipStream_t stream);
+int sl_sgd_flat_lars(float* w, const float* g, float* mom, uint16_t* shadow, long n, const int* step,
+                     const float* lr_tab, int lr_n, float lr, float mu, float wd, float wd_norm, float wd_bias,
+                     const uint8_t* cls, const uint16_t* tmap, const float* trust, int T, hipStream_t stream);
+
 // mlp_fused.hip
 long sl_mlp_x_tile_bytes(long rows);
 int sl_mlp_x_tile(const uint8_t* src, uint8_t* dst, long rows, hipStream_t stream);

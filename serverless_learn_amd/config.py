@@ -67,7 +67,10 @@ class Config:
     weight_decay: float = 0.0
     norm_weight_decay: float = -1.0    # resnet18: weight decay of the BatchNorm scales and shifts; -1 = weight_decay
     bias_weight_decay: float = -1.0    # weight decay of the other biases (fc.bias; the MLP's b1 b2 b3); -1 = weight_decay
-    optimizer: str = "sgd"             # sgd (momentum SGD) | adamw (beta1, beta2, adam_eps; decoupled weight_decay)
+    optimizer: str = "sgd"             # sgd (momentum SGD) | adamw (beta1, beta2, adam_eps; decoupled weight_decay) |
+                                       # lars (resnet18: momentum SGD under layer-wise trust ratios; lars_eta, lars_eps)
+    lars_eta: float = 0.001            # optimizer=lars: the trust coefficient (> 0)
+    lars_eps: float = 0.0              # optimizer=lars: added to the trust ratio's denominator (>= 0)
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-8
@@ -128,6 +131,13 @@ class Config:
         self._validate_classes()
         self._validate_decay_groups()
         self._validate_norm()
+        if self.optimizer == "lars" or (self.lars_eta, self.lars_eps) != (0.001, 0.0):  # NaN included
+            from .ops.optim import check_lars
+
+            check_lars(self.lars_eta, self.lars_eps)
+            if self.optimizer == "lars" and self.model in ("mlp", "simulate"):
+                raise ValueError(f"optimizer='lars': the {self.model} model has no per-tensor update to adapt "
+                                 "(model='resnet18')")
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")
         if isinstance(self.global_batch, bool) or int(self.global_batch) != self.global_batch or self.global_batch < 0:

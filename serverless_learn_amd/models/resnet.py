@@ -287,6 +287,7 @@ class ResNetModel:
 
     norm = "batch"
     norm_groups = 0
+    lars_capable = True  # optimizer="lars" (TrainerState): conv / fc weights adapted, norms and fc.bias not
 
     @property
     def n_params(self) -> int:

@@ -636,7 +636,13 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             O.sgd_flat(self.params, self.grad, self.mom, self.lr, self.momentum, self.weight_decay,
                        shadow=self.shadow)
             return
-        if self.opt.grouped:  # a weight decay per class (BatchNorm, fc.bias), read from the map
+        if self.opt.lars:  # chunk sums of squares, per-tensor trust ratios, the scaled update (lars.hip)
+            b = self.lars_buf
+            O.lars_norms(self.params, self.grad, b)
+            O.lars_trust(b, self.opt.lars_eta, self.opt.lars_eps, self.opt.weight_decay)
+            O.sgd_flat_lars(self.params, self.grad, self.mom, self.opt_step, self.lr_tab, b, self.opt.decays(),
+                            lr=self.lr, momentum=self.momentum, shadow=self.shadow)
+        elif self.opt.grouped:  # a weight decay per class (BatchNorm, fc.bias), read from the map
             if self.opt.adamw:
                 O.adamw_flat_groups(self.params, self.grad, self.mom, self.v, self.opt_step, self.opt, self.decay_cls,
                                     self.lr_tab, shadow=self.shadow)

@@ -15,8 +15,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, OptSpec, check_accum_steps, clip_buffers,
-                         clip_grad_, decay_vector, ema_update_, require_kernels, sgd_update, trainer_class_map)
+from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, LARS_KERNELS, LarsBuffers, OptSpec,
+                         check_accum_steps, clip_buffers, clip_grad_, decay_vector, ema_update_, lars_plan,
+                         require_kernels, sgd_update, trainer_class_map)
 
 
 @dataclass
@@ -47,6 +48,11 @@ class TrainerState:
     reference update takes.  Both follow from the model and the hyper-parameters: they are no
     state, and a trainer without groups has neither attribute.
 
+    Under ``optimizer="lars"`` (ResNet trainers) also ``lars_plan`` (ops/optim.py lars_plan: the
+    adapted tensors, their chunks and the block map) and on a GPU ``lars_buf``, its uploaded tables
+    with the launches' outputs; :meth:`trust_ratios` reads the last update's.  No state either: the
+    momentum is all that LARS keeps, so nothing new is checkpointed or broadcast.
+
     The owner sets ``params`` (``n_params`` real entries, then any padding) before
     :meth:`_init_state`, and keeps ``cursor`` (an int, or a 1-element tensor on the device)."""
 
@@ -54,6 +60,7 @@ class TrainerState:
     tickets = ()                  # of "opt_ticket" / "ema_ticket": the words the owner's launches use
     opt_kernels = ()              # entry points of the owner's step-counter rules
     group_kernels = ()            # ... and of those rules with decay groups on
+    lars_capable = False          # optimizer="lars": the ResNet trainers (models/resnet.py ResNetModel)
     accum_kernels = ACCUM_KERNELS  # ... and of its accumulated step
     graph = None                  # a captured step (GPU engines: a slot of utils/graphs.py)
     grad = None                   # the aggregated gradient of the last step, as the optimizer took it
@@ -68,7 +75,10 @@ class TrainerState:
         # accum_steps micro-batches per optimizer step: the gradient stays a mean over all of them
         self.accum_steps = check_accum_steps(accum_steps)
         self.opt = spec = OptSpec(lr=lr, momentum=momentum, weight_decay=weight_decay, **opt)
-        word = lambda: torch.zeros(1, dtype=torch.int32, device=self.device)  # noqa: E731
+        if spec.lars and not self.lars_capable:
+            raise ValueError("optimizer='lars' adapts the rate per weight tensor of a deep network: the mlp model's "
+                             "fused slab update cannot know a norm before it moves a weight (model='resnet18')")
+        word =lambda: torch.zeros(1, dtype=torch.int32, device=self.device)  # noqa: E731
         self.mom = torch.zeros_like(self.params) if (momentum > 0 or spec.adamw) else None
         # AdamW's second moment (mom is its first); the optimizer step the update reads (and the
         # ticket word of a launch that advances it itself) where the rule depends on the step
@@ -76,7 +86,8 @@ class TrainerState:
         self.opt_step = self.opt_ticket = self.lr_tab = None
         if not spec.plain:
             if self._gpu:
-                require_kernels(spec, *(self.group_kernels if spec.grouped else self.opt_kernels))
+                require_kernels(spec, *(LARS_KERNELS if spec.lars else
+                                        self.group_kernels if spec.grouped else self.opt_kernels))
             self.opt_step = word()
             self.opt_ticket = word() if "opt_ticket" in self.tickets else None
         self.clip_partials = self.clip_norm = self._grad_norm = None
@@ -90,6 +101,10 @@ class TrainerState:
             self.ema_ticket = word() if "ema_ticket" in self.tickets else None
         if spec.grouped:  # built once: the layout does not change
             self.decay_cls = torch.from_numpy(trainer_class_map(self)).to(self.device)
+        if spec.lars:  # likewise: the plan, on a GPU with its tables and the launches' outputs
+            self.lars_plan = lars_plan(self.layout(), int(self.params.numel()), self.norm_tensors())
+            self.lars_buf = LarsBuffers(self.lars_plan, self.device) if self._gpu else None
+            self._lars_rows = None  # CPU: the last update's (wn, gn, trust) rows
         self._opt_tables()
 
     def norm_tensors(self) -> tuple:
@@ -125,8 +140,12 @@ class TrainerState:
         if self.opt_step is None:
             sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
         else:
-            self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]),
-                            self.decay_vec if self.opt.grouped else None)
+            if self.opt.lars:
+                self._lars_rows = self.opt.update(self.params, self.mom, None, g, int(self.opt_step[0]),
+                                                  plan=self.lars_plan)
+            else:
+                self.opt.update(self.params, self.mom, self.v, g, int(self.opt_step[0]),
+                                self.decay_vec if self.opt.grouped else None)
             self.opt_step += 1
         if self.ema is not None:  # once per update, on the parameters just written
             t = min(int(self.ema_step[0]), self.ema_tab.numel() - 1)
@@ -139,6 +158,16 @@ class TrainerState:
         if not self.opt.clips or self.clip_norm is None:
             return self._grad_norm
         return float(self.clip_norm[0])
+
+    def trust_ratios(self) -> dict:
+        """``{tensor name: (wn, gn, trust)}`` of the last LARS update, for every adapted tensor (the
+        conv and linear weights); on a GPU one read from the device.  Empty before the first update
+        on the CPU, zeros on a GPU."""
+        if not self.opt.lars:
+            raise ValueError(f"this trainer's optimizer is {self.opt.optimizer!r}: only 'lars' has trust ratios")
+        if self._gpu:
+            return self.lars_buf.ratios()
+        return dict(zip(self.lars_plan.names, self._lars_rows or ()))
 
     def ema_flat(self) -> torch.Tensor:
         """A copy of the averaged parameters (``ema_decay > 0``)."""

@@ -20,6 +20,12 @@ torchvision's ``set_weight_decay``): :func:`decay_class_map` gives every 64-elem
 trainer's flat vector its class, :func:`decay_vector` the per-element decay the reference rules
 take, and the ``*_groups`` launches read the same map on the device.
 
+``optimizer="lars"`` (ResNet trainers) is momentum SGD whose decayed gradient is scaled per weight
+tensor by a trust ratio of the tensor's and its gradient's norms: :func:`lars_update` is its
+reference, :func:`lars_plan` cuts the flat vector into the chunks whose sums of squares
+:func:`lars_norms` takes, :func:`lars_trust` folds them per tensor and :func:`sgd_flat_lars` is the
+update launch (csrc/kernels/lars.hip).
+
 A weight EMA (``ema_decay``) follows every update: :func:`ema_update_` is its reference,
 :func:`ema_table` the per-step coefficients and :func:`ema_flat` the one launch that applies them and
 advances its own device-resident counter.
@@ -34,7 +40,7 @@ import torch
 
 from . import _native as N
 
-OPTIMIZERS = ("sgd", "adamw")
+OPTIMIZERS = ("sgd", "adamw", "lars")
 SCHEDULES = ("constant", "linear", "cosine")
 
 # update-kernel rules (csrc/kernels/mlp_fused.hip)
@@ -146,6 +152,91 @@ def decay_vector(cls, n: int, decays, device="cpu") -> torch.Tensor:
     return torch.tensor([float(d) for d in decays], dtype=torch.float64)[per].to(device)
 
 
+# ---- LARS: layer-wise trust ratios (You et al. 2017; apex LARC's scaling without its clip) ----
+LARS_CHUNK = 4096     # elements per chunk of the norms launch (csrc/kernels/lars.hip LARS_CHUNK)
+LARS_NO_TENSOR = 0xFFFF  # block-map entry of a block no adapted tensor owns
+
+
+def check_lars(eta, eps) -> None:
+    """``lars_eta``: a finite float > 0; ``lars_eps``: a finite float >= 0."""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)  # noqa: E731
+    if not num(eta) or eta <= 0:
+        raise ValueError(f"lars_eta must be a finite number > 0, got {eta!r}")
+    if not num(eps) or eps < 0:
+        raise ValueError(f"lars_eps must be a finite number >= 0, got {eps!r}")
+
+
+@dataclass(frozen=True)
+class LarsPlan:
+    """:func:`lars_plan`'s result.  ``names``: the T adapted tensors (class 0: conv and linear
+    weights) in offset order; ``tensors``: int32 ``[T][4]`` = (offset, numel, first chunk, chunk
+    count); ``chunks``: int32 ``[C][2]`` = (offset, count); ``block_map``: uint16 per 64-element
+    block, the adapted tensor that owns it or :data:`LARS_NO_TENSOR`; ``cls``: the
+    :func:`decay_class_map` of the same layout; ``n``: the vector's length."""
+    names: tuple
+    tensors: np.ndarray
+    chunks: np.ndarray
+    block_map: np.ndarray
+    cls: np.ndarray
+    n: int
+
+
+def lars_plan(layout, n: int, norm=()) -> LarsPlan:
+    """How the LARS launches see a flat vector of ``n`` elements (``layout``, ``norm``: as for
+    :func:`decay_class_map`, which is asserted).  Every class-0 tensor is adapted: its real
+    elements ``[off, off + numel)`` are cut into consecutive chunks of at most :data:`LARS_CHUNK`
+    elements, none straddling a tensor, each starting on a 16-byte boundary (tensors start on
+    64-element boundaries), only a tensor's last with a count that is no multiple of 4.  Padding
+    belongs to the tensor it follows in the block map, and is in no chunk."""
+    n = int(n)
+    assert 0 < n < 2 ** 31, "the chunk table holds int32 offsets"
+    cls = decay_class_map(layout, n, norm)
+    entries = sorted(layout, key=lambda e: e[2])
+    names, tensors, chunks = [], [], []
+    block_map = np.full(cls.shape, LARS_NO_TENSOR, dtype=np.uint16)
+    for i, (name, shape, off) in enumerate(entries):
+        numel = math.prod(shape)
+        if cls[off // DECAY_BLOCK] != CLS_WEIGHT or numel == 0:
+            continue
+        end = entries[i + 1][2] if i + 1 < len(entries) else n
+        block_map[off // DECAY_BLOCK:(end + DECAY_BLOCK - 1) // DECAY_BLOCK] = len(names)
+        first = len(chunks)
+        chunks += [(o, min(LARS_CHUNK, off + numel - o)) for o in range(off, off + numel, LARS_CHUNK)]
+        tensors.append((off, numel, first, len(chunks) - first))
+        names.append(name)
+    assert 0 < len(names) < LARS_NO_TENSOR, "the block map names a tensor in 16 bits"
+    return LarsPlan(tuple(names), np.array(tensors, dtype=np.int32).reshape(-1, 4),
+                    np.array(chunks, dtype=np.int32).reshape(-1, 2), block_map, cls, n)
+
+
+def lars_update(flat, mom, grad, lr_t, momentum, decay, tensors: LarsPlan, eta, eps, trust=None) -> list:
+    """The LARS reference, in place, in float64 on the fp32 state (each stored value rounded once).
+    For every adapted tensor ``T`` of the plan ``tensors``, over its real elements: ``wn = ||w||``,
+    ``gn = ||g||``, ``trust_T = eta wn / (gn + wd wn + eps)`` where both norms are positive and 1
+    otherwise, with ``wd = decay[0]``; every other element has trust 1.  Then element-wise, with
+    ``c`` the element's class: ``d = trust_T (g + decay[c] w)``, ``mom = momentum mom + d``,
+    ``w -= lr_t mom`` (``mom`` None: ``w -= lr_t d``).  Returns ``(wn, gn, trust)`` per adapted
+    tensor, in the plan's order.  ``trust``: ratios to apply in place of the computed ones (a GPU
+    test passes the kernel's own fp32 values, so that its element-wise bound holds no norm error)."""
+    plan = tensors
+    n = plan.n
+    w, g = flat[:n].double(), grad[:n].double()
+    rows = []
+    for t, (off, numel, _, _) in enumerate(plan.tensors.tolist()):
+        wn = float(torch.linalg.vector_norm(w[off:off + numel]))
+        gn = float(torch.linalg.vector_norm(g[off:off + numel]))
+        tr = eta * wn / (gn + float(decay[0]) * wn + eps) if wn > 0 and gn > 0 else 1.0
+        rows.append((wn, gn, tr if trust is None else float(trust[t])))
+    scale = torch.tensor([r[2] for r in rows] + [1.0], dtype=torch.float64)
+    owner = torch.as_tensor(plan.block_map.astype(np.int64)).clamp_(max=len(rows))
+    d = scale[owner.repeat_interleave(DECAY_BLOCK)[:n]] * (g + decay_vector(plan.cls, n, decay) * w)
+    if mom is not None:
+        d = momentum * mom[:n].double() + d
+        mom[:n] = d.to(mom.dtype)
+    flat[:n] = (w - lr_t * d).to(flat.dtype)
+    return rows
+
+
 CLIP_EPS = 1e-6  # torch.nn.utils.clip_grad_norm_'s constant
 
 
@@ -238,12 +329,16 @@ class OptSpec:
     # either switches the decay groups on, even to weight_decay's own value
     norm_weight_decay: float | None = None
     bias_weight_decay: float | None = None
+    # optimizer="lars": the trust coefficient, and a constant added to the trust ratio's denominator
+    lars_eta: float = 0.001
+    lars_eps: float = 0.0
 
     def __post_init__(self):
         check_group_decay("norm_weight_decay", self.norm_weight_decay)
         check_group_decay("bias_weight_decay", self.bias_weight_decay)
         if self.optimizer not in OPTIMIZERS:
             raise ValueError(f"unknown optimizer {self.optimizer!r} (choose from {OPTIMIZERS})")
+        check_lars(self.lars_eta, self.lars_eps)
         if self.lr_schedule not in SCHEDULES:
             raise ValueError(f"unknown lr_schedule {self.lr_schedule!r} (choose from {SCHEDULES})")
         if self.lr_warmup_steps < 0 or self.lr_decay_steps < 0:
@@ -274,8 +369,18 @@ class OptSpec:
         return self.optimizer == "adamw"
 
     @property
+    def lars(self) -> bool:
+        return self.optimizer == "lars"
+
+    @property
     def scheduled(self) -> bool:
         return self.lr_schedule != "constant" or self.lr_warmup_steps > 0
+
+    @property
+    def mapped(self) -> bool:
+        """The update reads the class map: decay groups on, or LARS (whose exclusion list the
+        classes are), whether or not a class decay is set."""
+        return self.grouped or self.lars
 
     @property
     def grouped(self) -> bool:
@@ -293,8 +398,9 @@ class OptSpec:
         """Momentum SGD at a fixed lr without decay groups: the rule without a step counter.  A
         grouped trainer always runs a step-counter rule (a grouped SGD trainer at a fixed lr runs
         ``RULE_SGD_LR`` with no table, which reads the scalar lr), so it has an ``opt_step``, and
-        the plain rule's kernels and launches are what they were before groups existed."""
-        return not self.adamw and not self.scheduled and not self.grouped
+        the plain rule's kernels and launches are what they were before groups existed.  Nor is a
+        LARS trainer ever plain."""
+        return not self.adamw and not self.scheduled and not self.grouped and not self.lars
 
     @property
     def rule(self) -> int:
@@ -321,9 +427,15 @@ class OptSpec:
         return (self.beta1, self.beta2, 1.0 - self.beta1, 1.0 - self.beta2, math.log(self.beta1),
                 math.log(self.beta2), self.adam_eps)
 
-    def update(self, flat, mom, v, grad, step: int, decay=None) -> None:
+    def update(self, flat, mom, v, grad, step: int, decay=None, plan=None):
         """One reference update of 0-based ``step``, in place (the CPU trainers' optimizer).
-        ``decay``: the per-element weight decay of a grouped spec (:func:`decay_vector`)."""
+        ``decay``: the per-element weight decay of a grouped spec (:func:`decay_vector`).
+        ``plan``: the :func:`lars_plan` of a LARS spec, which takes the class decays from
+        :meth:`decays` and returns :func:`lars_update`'s ``(wn, gn, trust)`` rows."""
+        if self.lars:
+            assert plan is not None, "a LARS spec updates with its plan"
+            return lars_update(flat, mom, grad, self.lr_at(step), self.momentum, self.decays(), plan,
+                               self.lars_eta, self.lars_eps)
         assert (decay is not None) == self.grouped, "a grouped spec updates with its decay vector"
         wd = self.weight_decay if decay is None else decay
         if self.adamw:
@@ -346,6 +458,8 @@ class OptSpec:
             d["norm_weight_decay"] = self.norm_weight_decay
         if self.bias_weight_decay is not None:
             d["bias_weight_decay"] = self.bias_weight_decay
+        if self.lars:
+            d.update(lars_eta=self.lars_eta, lars_eps=self.lars_eps)
         return d
 
 
@@ -430,6 +544,67 @@ def adamw_flat_groups(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torc
     N.call("sl_adamw_flat_groups", N.ptr(w), N.ptr(g), N.ptr(m), N.ptr(v), N.ptr(shadow), w.numel(), N.ptr(step),
            N.ptr(lr_tab), lr_tab.numel() if lr_tab is not None else 0, float(spec.lr), wd, float(grad_scale),
            *spec.adam_scalars(), N.ptr(cls), wd_norm, wd_bias, N.stream_ptr())
+
+
+LARS_KERNELS = ("sl_lars_chunk", "sl_lars_norms", "sl_lars_trust", "sl_sgd_flat_lars")
+
+
+class LarsBuffers:
+    """A :class:`LarsPlan` on a device, uploaded once: the chunk and tensor tables, the block map
+    and the class map, and what the launches write, ``partials`` (fp64 ``[C][2]``) and ``out``
+    (fp32 ``[T][3]`` = (wn, gn, trust) of the last update)."""
+
+    def __init__(self, plan: LarsPlan, device):
+        assert int(N.lib().sl_lars_chunk()) == LARS_CHUNK, "the kernel library was built with another LARS_CHUNK"
+        up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+        self.plan = plan
+        self.chunks, self.tensors = up(plan.chunks), up(plan.tensors)
+        # (torch has no uint16 arithmetic, and needs none: the map is only handed to the kernel)
+        self.block_map = up(plan.block_map.view(np.int16))
+        self.cls = up(plan.cls)
+        self.partials = torch.zeros(len(plan.chunks), 2, dtype=torch.float64, device=device)
+        self.out = torch.zeros(len(plan.names), 3, dtype=torch.float32, device=device)
+
+    def ratios(self) -> dict:
+        """``{tensor name: (wn, gn, trust)}`` of the last update (one read from the device)."""
+        return {name: tuple(row) for name, row in zip(self.plan.names, self.out.tolist())}
+
+
+def _check_lars(w: torch.Tensor, g: torch.Tensor, b: LarsBuffers) -> None:
+    assert w.is_cuda and w.dtype == torch.float32 and g.dtype == torch.float32
+    assert w.is_contiguous() and g.is_contiguous() and g.numel() == w.numel()
+    assert w.numel() == b.plan.n, "the plan was made for a vector of another length"  # (every chunk is inside it)
+    assert b.chunks.device == w.device
+
+
+def lars_norms(w: torch.Tensor, g: torch.Tensor, b: LarsBuffers) -> None:
+    """``b.partials[c] = (sum w^2, sum g^2)`` over chunk ``c`` of the plan: one launch, one
+    workgroup per chunk, fp64 sums in a fixed order (csrc/kernels/lars.hip lars_norms_kernel)."""
+    _check_lars(w, g, b)
+    N.call("sl_lars_norms", N.ptr(w), N.ptr(g), N.ptr(b.chunks), b.chunks.shape[0], N.ptr(b.partials), N.stream_ptr())
+
+
+def lars_trust(b: LarsBuffers, eta: float, eps: float, weight_decay: float) -> None:
+    """``b.out[t] = (wn, gn, trust)`` of every adapted tensor from ``b.partials``: one wave per
+    tensor, formed in fp64 and rounded once (lars_trust_kernel)."""
+    N.call("sl_lars_trust", N.ptr(b.partials), N.ptr(b.tensors), b.tensors.shape[0], float(eta), float(eps),
+           float(weight_decay), N.ptr(b.out), N.stream_ptr())
+
+
+def sgd_flat_lars(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor | None, step: torch.Tensor,
+                  lr_tab: torch.Tensor | None, b: LarsBuffers, decays, lr: float = 0.0, momentum: float = 0.0,
+                  shadow: torch.Tensor | None = None) -> None:
+    """The LARS update launch (lars_update_kernel): :func:`sgd_flat_lr_groups` with the decayed
+    gradient of element ``i`` scaled by ``b.out[b.block_map[i // 64]]``'s trust (1 where no tensor
+    owns the block).  The caller advances ``step``."""
+    _check_flat(w, g, shadow)
+    _check_lars(w, g, b)
+    assert step.dtype == torch.int32 and (lr_tab is None or lr_tab.dtype == torch.float32)
+    assert mom is None or (mom.dtype == torch.float32 and mom.numel() == w.numel())
+    wd, wd_norm, wd_bias = (float(d) for d in decays)
+    N.call("sl_sgd_flat_lars", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), N.ptr(step), N.ptr(lr_tab),
+           lr_tab.numel() if lr_tab is not None else 0, float(lr), float(momentum), wd, wd_norm, wd_bias,
+           N.ptr(b.cls), N.ptr(b.block_map), N.ptr(b.out), b.tensors.shape[0], N.stream_ptr())
 
 
 def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:

@@ -172,6 +172,8 @@ class Worker:
             kw.update(ema_decay=c.ema_decay, ema_warmup=c.ema_warmup)
         if c.n_classes != 10:  # (Config refuses anything but ten for the MLP)
             kw.update(classes=c.n_classes)
+        if c.optimizer == "lars":
+            kw.update(lars_eta=c.lars_eta, lars_eps=c.lars_eps)
         kw.update(c.decay_groups)  # norm_weight_decay / bias_weight_decay, where set
         if c.norm != "batch":  # (a stem or input size it does not serve is refused by the trainer)
             kw.update(norm=c.norm, norm_groups=c.norm_groups)
@@ -185,8 +187,10 @@ class Worker:
             counts = decay_class_counts(t.decay_cls.cpu().numpy(), t.n_params)
             self.log.info("decay_groups", **{f"{k}_decay": d for k, d in zip(DECAY_CLASSES, t.opt.decays())},
                           **{f"{k}_elements": n for k, n in zip(DECAY_CLASSES, counts)})
+        if c.optimizer == "lars":
+            self.log.info("lars", eta=c.lars_eta, eps=c.lars_eps, tensors=len(self.trainer.lars_plan.names))
         if c.ema_decay != 0:
-            self.log.info("ema", decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
+            self.log.info("ema",decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
         if self.cfg.sync in ("gossip", "ps"):
             self.gossip = GossipState(self._flat_view(), self.cfg.learn_rate, self.cfg.gossip_compat)
 
