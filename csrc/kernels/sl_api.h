@@ -195,6 +195,23 @@ int sl_sgd_flat_lars(float* w, const float* g, float* mom, uint16_t* shadow, lon
                      const float* lr_tab, int lr_n, float lr, float mu, float wd, float wd_norm, float wd_bias,
                      const uint8_t* cls, const uint16_t* tmap, const float* trust, int T, hipStream_t stream);
 
+// muon.hip: grouped Newton-Schulz orthogonalisation of the ResNet trainers' conv momenta (optimizer="muon")
+int sl_muon_chunk();
+int sl_muon_prep(const float* g, float* mom, const int* chunks, int n_chunks, float mu, int nesterov,
+                 double* partials, const int* tensors_h, const int* tensors, int T, const int* tiles, int n_tiles,
+                 uint16_t* x0, float* norms, hipStream_t stream);
+int sl_muon_gram(const uint16_t* x, const int* tensors_h, const int* tensors, int T, const int* gtiles, int n_gtiles,
+                 float* ws, const int* ttiles, int n_ttiles, uint16_t* a, hipStream_t stream);
+int sl_muon_poly(const uint16_t* a, const int* tensors_h, const int* tensors, int T, const int* tiles, int n_tiles,
+                 uint16_t* b, hipStream_t stream);
+int sl_muon_apply(const uint16_t* xin, const uint16_t* b, const int* tensors_h, const int* tensors, int T,
+                  const int* tiles, int n_tiles, uint16_t* xout, hipStream_t stream);
+int sl_sgd_flat_muon(float* w, const float* g, float* mom, uint16_t* shadow, long n, const int* step,
+                     const float* lr_tab, int lr_n, float lr, float mu, float wd, float wd_norm, float wd_bias,
+                     float gscale, float ratio, const uint8_t* cls, const uint16_t* tmap, const int* tensors_h,
+                     const int* tensors, int T, const uint16_t* x0, const uint16_t* x1, int steps,
+                     hipStream_t stream);
+
 // mlp_fused.hip
 long sl_mlp_x_tile_bytes(long rows);
 int sl_mlp_x_tile(const uint8_t* src, uint8_t* dst, long rows, hipStream_t stream);

@@ -71,6 +71,10 @@ class Config:
                                        # lars (resnet18: momentum SGD under layer-wise trust ratios; lars_eta, lars_eps)
     lars_eta: float = 0.001            # optimizer=lars: the trust coefficient (> 0)
     lars_eps: float = 0.0              # optimizer=lars: added to the trust ratio's denominator (>= 0)
+                                       # muon (resnet18: conv momenta orthogonalised by Newton-Schulz iterations)
+    muon_lr_ratio: float = 1.0         # optimizer=muon: the Muon tensors' learning rate over the schedule's (> 0)
+    muon_nesterov: bool = True         # optimizer=muon: orthogonalise g + mu mom (else mom)
+    muon_ns_steps: int = 5             # optimizer=muon: Newton-Schulz iterations (1..8)
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-8
@@ -137,6 +141,13 @@ class Config:
             check_lars(self.lars_eta, self.lars_eps)
             if self.optimizer == "lars" and self.model in ("mlp", "simulate"):
                 raise ValueError(f"optimizer='lars': the {self.model} model has no per-tensor update to adapt "
+                                 "(model='resnet18')")
+        if self.optimizer == "muon" or (self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps) != (1.0, True, 5):
+            from .ops.optim import check_muon
+
+            check_muon(self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps)
+            if self.optimizer == "muon" and self.model in ("mlp", "simulate"):
+                raise ValueError(f"optimizer='muon': the {self.model} model has no conv weight to orthogonalise "
                                  "(model='resnet18')")
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")

@@ -379,7 +379,7 @@ class FusedMLPTrainer(GraphedStep, TrainerState):
         new = dataclasses.replace(self.opt, **kw)
         if new.grouped != self.opt.grouped:  # (it would also change the rule: a grouped trainer is never plain)
             raise ValueError("decay groups are switched on or off at construction (build a new trainer)")
-        if (new.adamw, new.lars, new.plain) != (self.opt.adamw, self.opt.lars, self.opt.plain):
+        if (new.adamw, new.lars, new.muon, new.plain) != (self.opt.adamw, self.opt.lars, self.opt.muon, self.opt.plain):
             raise ValueError("the optimizer rule is fixed at construction (build a new trainer)")
         if new.emas != self.opt.emas:
             raise ValueError("the weight EMA is switched on or off at construction (build a new trainer)")

@@ -287,7 +287,9 @@ class ResNetModel:
 
     norm = "batch"
     norm_groups = 0
-    lars_capable = True  # optimizer="lars" (TrainerState): conv / fc weights adapted, norms and fc.bias not
+    # optimizer="lars" (TrainerState): conv / fc weights adapted, norms and fc.bias not; and optimizer="muon": the
+    # conv weights but the stem's orthogonalised
+    lars_capable = True
 
     @property
     def n_params(self) -> int:

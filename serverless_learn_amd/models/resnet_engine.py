@@ -642,6 +642,12 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             O.lars_trust(b, self.opt.lars_eta, self.opt.lars_eps, self.opt.weight_decay)
             O.sgd_flat_lars(self.params, self.grad, self.mom, self.opt_step, self.lr_tab, b, self.opt.decays(),
                             lr=self.lr, momentum=self.momentum, shadow=self.shadow)
+        elif self.opt.muon:  # momentum and X0, the Newton-Schulz iterations, the update (muon.hip)
+            b, s = self.muon_buf, self.opt
+            O.muon_orthogonalize(self.grad, self.mom, b, self.momentum, s.muon_nesterov, s.muon_ns_steps)
+            O.sgd_flat_muon(self.params, self.grad, self.mom, self.opt_step, self.lr_tab, b, s.decays(), lr=self.lr,
+                            momentum=self.momentum, lr_ratio=s.muon_lr_ratio, ns_steps=s.muon_ns_steps,
+                            shadow=self.shadow)
         elif self.opt.grouped:  # a weight decay per class (BatchNorm, fc.bias), read from the map
             if self.opt.adamw:
                 O.adamw_flat_groups(self.params, self.grad, self.mom, self.v, self.opt_step, self.opt, self.decay_cls,

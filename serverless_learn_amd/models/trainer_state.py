@@ -15,9 +15,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, LARS_KERNELS, LarsBuffers, OptSpec,
-                         check_accum_steps, clip_buffers, clip_grad_, decay_vector, ema_update_, lars_plan,
-                         require_kernels, sgd_update, trainer_class_map)
+from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, LARS_KERNELS, MUON_KERNELS, LarsBuffers,
+                         MuonBuffers, OptSpec, check_accum_steps, clip_buffers, clip_grad_, decay_vector, ema_update_,
+                         lars_plan, muon_plan, require_kernels, sgd_update, trainer_class_map)
 
 
 @dataclass
@@ -53,6 +53,12 @@ class TrainerState:
     with the launches' outputs; :meth:`trust_ratios` reads the last update's.  No state either: the
     momentum is all that LARS keeps, so nothing new is checkpointed or broadcast.
 
+    Under ``optimizer="muon"`` (ResNet trainers) likewise ``muon_plan`` (ops/optim.py muon_plan: the
+    Muon tensors, the block map and the grouped launches' tile tables) and on a GPU ``muon_buf``, the
+    uploaded tables with the work buffers (two bf16 copies of the Muon tensors, the Gram matrices, the
+    split-K partials); :meth:`muon_norms` reads the last update's ``||u||_F``.  The momentum, always
+    allocated under Muon, is its only state.
+
     The owner sets ``params`` (``n_params`` real entries, then any padding) before
     :meth:`_init_state`, and keeps ``cursor`` (an int, or a 1-element tensor on the device)."""
 
@@ -78,15 +84,18 @@ class TrainerState:
         if spec.lars and not self.lars_capable:
             raise ValueError("optimizer='lars' adapts the rate per weight tensor of a deep network: the mlp model's "
                              "fused slab update cannot know a norm before it moves a weight (model='resnet18')")
+        if spec.muon and not self.lars_capable:
+            raise ValueError("optimizer='muon' orthogonalises the momentum of a deep network's conv weights: the mlp "
+                             "model's fused slab update has no per-tensor step (model='resnet18')")
         word =lambda: torch.zeros(1, dtype=torch.int32, device=self.device)  # noqa: E731
-        self.mom = torch.zeros_like(self.params) if (momentum > 0 or spec.adamw) else None
+        self.mom = torch.zeros_like(self.params) if (momentum > 0 or spec.adamw or spec.muon) else None
         # AdamW's second moment (mom is its first); the optimizer step the update reads (and the
         # ticket word of a launch that advances it itself) where the rule depends on the step
         self.v = torch.zeros_like(self.params) if spec.adamw else None
         self.opt_step = self.opt_ticket = self.lr_tab = None
         if not spec.plain:
             if self._gpu:
-                require_kernels(spec, *(LARS_KERNELS if spec.lars else
+                require_kernels(spec, *(LARS_KERNELS if spec.lars else MUON_KERNELS if spec.muon else
                                         self.group_kernels if spec.grouped else self.opt_kernels))
             self.opt_step = word()
             self.opt_ticket = word() if "opt_ticket" in self.tickets else None
@@ -105,6 +114,10 @@ class TrainerState:
             self.lars_plan = lars_plan(self.layout(), int(self.params.numel()), self.norm_tensors())
             self.lars_buf = LarsBuffers(self.lars_plan, self.device) if self._gpu else None
             self._lars_rows = None  # CPU: the last update's (wn, gn, trust) rows
+        if spec.muon:  # the plan, and on a GPU its tables and work buffers: allocated under Muon only
+            self.muon_plan = muon_plan(self.layout(), int(self.params.numel()), self.norm_tensors())
+            self.muon_buf = MuonBuffers(self.muon_plan, self.device) if self._gpu else None
+            self._muon_norms = None  # CPU: the last update's ||u||_F per tensor
         self._opt_tables()
 
     def norm_tensors(self) -> tuple:
@@ -140,7 +153,10 @@ class TrainerState:
         if self.opt_step is None:
             sgd_update(self.params, self.mom, g, self.lr, self.momentum, self.weight_decay)
         else:
-            if self.opt.lars:
+            if self.opt.muon:
+                self._muon_norms = self.opt.update(self.params, self.mom, None, g, int(self.opt_step[0]),
+                                                   plan=self.muon_plan)
+            elif self.opt.lars:
                 self._lars_rows = self.opt.update(self.params, self.mom, None, g, int(self.opt_step[0]),
                                                   plan=self.lars_plan)
             else:
@@ -168,6 +184,16 @@ class TrainerState:
         if self._gpu:
             return self.lars_buf.ratios()
         return dict(zip(self.lars_plan.names, self._lars_rows or ()))
+
+    def muon_norms(self) -> dict:
+        """``{tensor name: ||u||_F}`` of the last Muon update, for every Muon tensor (the conv weights
+        but the stem's); on a GPU one read from the device.  Empty before the first update on the
+        CPU, zeros on a GPU."""
+        if not self.opt.muon:
+            raise ValueError(f"this trainer's optimizer is {self.opt.optimizer!r}: only 'muon' has Muon norms")
+        if self._gpu:
+            return dict(zip(self.muon_plan.names, self.muon_buf.norms.tolist()))
+        return dict(zip(self.muon_plan.names, self._muon_norms or ()))
 
     def ema_flat(self) -> torch.Tensor:
         """A copy of the averaged parameters (``ema_decay > 0``)."""

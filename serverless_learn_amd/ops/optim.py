@@ -26,6 +26,13 @@ reference, :func:`lars_plan` cuts the flat vector into the chunks whose sums of 
 :func:`lars_norms` takes, :func:`lars_trust` folds them per tensor and :func:`sgd_flat_lars` is the
 update launch (csrc/kernels/lars.hip).
 
+``optimizer="muon"`` (ResNet trainers) keeps momentum SGD's state, but updates every conv weight
+but the stem's, seen as the matrix ``[cout, k k cin]`` the flat vector stores, with its momentum
+orthogonalised by Newton-Schulz iterations in bf16: :func:`newton_schulz` and :func:`muon_update`
+are the reference, :func:`muon_plan` the host side (tensors, block map, tile tables) and
+:func:`muon_prep`, :func:`muon_gram`, :func:`muon_poly`, :func:`muon_apply` and
+:func:`sgd_flat_muon` the grouped launches (csrc/kernels/muon.hip).
+
 A weight EMA (``ema_decay``) follows every update: :func:`ema_update_` is its reference,
 :func:`ema_table` the per-step coefficients and :func:`ema_flat` the one launch that applies them and
 advances its own device-resident counter.
@@ -40,7 +47,7 @@ import torch
 
 from . import _native as N
 
-OPTIMIZERS = ("sgd", "adamw", "lars")
+OPTIMIZERS = ("sgd", "adamw", "lars", "muon")
 SCHEDULES = ("constant", "linear", "cosine")
 
 # update-kernel rules (csrc/kernels/mlp_fused.hip)
@@ -237,6 +244,157 @@ def lars_update(flat, mom, grad, lr_t, momentum, decay, tensors: LarsPlan, eta, 
     return rows
 
 
+# ---- Muon: momentum orthogonalised by Newton-Schulz (Jordan et al. 2024) ----
+NS_COEFFS = (3.4445, -4.7750, 2.0315)  # (a, b, c) of X <- a X + (b A + c A A) X, A = X X^T
+MUON_EPS = 1e-7       # added to ||u||_F
+MUON_TILE = 64        # both sides of a Muon tensor are multiples of it (csrc/kernels/muon.hip MU_TILE)
+MUON_CHUNK = MUON_TILE * MUON_TILE  # elements per chunk of the momentum launch (sl_muon_chunk)
+MUON_MAX_SIDE = 512   # the working (wide-orientation) row count's limit
+MUON_KSLICE = 512     # columns per split-K slice of the Gram launch
+MUON_EXCLUDE = ("stem.weight", "fc.weight")  # multi-dimensional weights that stay on the SGD rule
+
+
+def check_muon(lr_ratio, nesterov, ns_steps) -> None:
+    """``muon_lr_ratio``: a finite float > 0; ``muon_nesterov``: a bool; ``muon_ns_steps``: an
+    integer in 1..8."""
+    r = lr_ratio
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not math.isfinite(r) or r <= 0:
+        raise ValueError(f"muon_lr_ratio must be a finite number > 0, got {r!r}")
+    if not isinstance(nesterov, (bool, np.bool_)):
+        raise ValueError(f"muon_nesterov must be a bool, got {nesterov!r}")
+    k = ns_steps
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 8:
+        raise ValueError(f"muon_ns_steps must be an integer in 1..8, got {k!r}")
+
+
+def _bf16(x: torch.Tensor) -> torch.Tensor:
+    return x.float().bfloat16().double()
+
+
+def newton_schulz(u: torch.Tensor, steps: int = 5, emulate: bool = False) -> torch.Tensor:
+    """``steps`` Newton-Schulz iterations on the matrix ``u``, in float64: ``X = u / (||u||_F +
+    1e-7)``, transposed if it is tall, then ``A = X X^T``, ``B = b A + c A A``, ``X = a X + B X``
+    with :data:`NS_COEFFS`, transposed back.  ``emulate``: round to bf16 at the four stores the
+    kernels make (X0, A, B and every X); without it nothing is rounded."""
+    a, b, c = NS_COEFFS
+    rnd = _bf16 if emulate else (lambda x: x)
+    u = u.double()
+    X = rnd(u / (torch.linalg.vector_norm(u) + MUON_EPS))
+    tall = X.shape[0] > X.shape[1]
+    if tall:
+        X = X.T
+    for _ in range(int(steps)):
+        A = rnd(X @ X.T)
+        B = rnd(b * A + c * (A @ A))
+        X = rnd(a * X + B @ X)
+    return (X.T if tall else X).contiguous()
+
+
+def fma32(a: float, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """fp32 ``fma(a, x, y)`` of fp32 tensors, exactly: the product is exact in float64, the sum is
+    rounded to odd there (its TwoSum error says which way), and float64 -> fp32 rounds once."""
+    p, y = float(np.float32(a)) * x.double(), y.double()
+    s = p + y
+    bb = s - p
+    err = (p - (s - bb)) + (y - bb)
+    odd = (err != 0) & ((s.view(torch.int64) & 1) == 0)
+    toward = torch.where(err > 0, math.inf, -math.inf).to(torch.float64)
+    return torch.where(odd, torch.nextafter(s, toward), s).float()
+
+
+@dataclass(frozen=True)
+class MuonPlan:
+    """:func:`muon_plan`'s result.  ``names``: the T Muon tensors in offset order; ``tensors``:
+    int32 ``[T][12]`` = (offset, m, n, transposed, x offset, a offset, partials offset, slices,
+    first chunk, chunk count, columns per slice, 0), where the work buffers hold tensor ``t`` in
+    the wide orientation (``min(m, n)`` rows) at ``x offset``, its Gram matrices at ``a offset``
+    and its split-K partials at ``partials offset``; ``chunks``: int32 ``[C]`` offsets of
+    :data:`MUON_CHUNK` elements; ``block_map``: as :class:`LarsPlan`'s; ``cls``: the
+    :func:`decay_class_map`; the int32 ``[.][4]`` tile tables ``tiles`` (tensor, i, j, 0: every
+    64 x 64 tile of every X), ``gram_tiles`` (tensor, i, j <= i, slice), ``tri_tiles`` (tensor, i,
+    j <= i, 0) and ``poly_tiles`` (tensor, i, j, 0); ``x_elems``, ``a_elems``, ``ws_floats``: the
+    work buffers' sizes; ``n``: the vector's length."""
+    names: tuple
+    tensors: np.ndarray
+    chunks: np.ndarray
+    block_map: np.ndarray
+    cls: np.ndarray
+    tiles: np.ndarray
+    gram_tiles: np.ndarray
+    tri_tiles: np.ndarray
+    poly_tiles: np.ndarray
+    x_elems: int
+    a_elems: int
+    ws_floats: int
+    n: int
+
+
+def muon_plan(layout, n: int, norm=(), exclude=MUON_EXCLUDE) -> MuonPlan:
+    """How the Muon launches see a flat vector of ``n`` elements (``layout``, ``norm``: as for
+    :func:`decay_class_map`).  Every class-0 tensor of two or more dimensions that ``exclude`` does
+    not name is a Muon tensor, the matrix ``[shape[0], prod(shape[1:])]``; both sides must be
+    multiples of :data:`MUON_TILE` and the smaller at most :data:`MUON_MAX_SIDE` (ValueError)."""
+    n = int(n)
+    assert 0 < n < 2 ** 31, "the tables hold int32 offsets"
+    cls = decay_class_map(layout, n, norm)
+    names, tensors, chunks = [], [], []
+    tiles, gram, tri, poly = [], [], [], []
+    block_map = np.full(cls.shape, LARS_NO_TENSOR, dtype=np.uint16)
+    xoff = aoff = poff = 0
+    for name, shape, off in sorted(layout, key=lambda e: e[2]):
+        if len(shape) < 2 or name in exclude or cls[off // DECAY_BLOCK] != CLS_WEIGHT:
+            continue
+        m, k = int(shape[0]), math.prod(shape[1:])
+        rows, cols = min(m, k), max(m, k)
+        if m % MUON_TILE or k % MUON_TILE or not 0 < rows <= MUON_MAX_SIDE:
+            raise ValueError(f"muon: {name} is {m} x {k}: both sides must be multiples of {MUON_TILE} and the "
+                             f"smaller at most {MUON_MAX_SIDE}")
+        t, kslice = len(names), min(MUON_KSLICE, cols)
+        slices, rt, ct = -(-cols // kslice), rows // MUON_TILE, cols // MUON_TILE
+        block_map[off // DECAY_BLOCK:(off + m * k) // DECAY_BLOCK] = t
+        tensors.append((off, m, k, int(m > k), xoff, aoff, poff, slices, len(chunks), m * k // MUON_CHUNK, kslice, 0))
+        chunks += range(off, off + m * k, MUON_CHUNK)
+        tiles += [(t, i, j, 0) for i in range(rt) for j in range(ct)]
+        tri += [(t, i, j, 0) for i in range(rt) for j in range(i + 1)]
+        gram += [(t, i, j, s) for s in range(slices) for i in range(rt) for j in range(i + 1)]
+        poly += [(t, i, j, 0) for i in range(rt) for j in range(rt)]
+        names.append(name)
+        xoff, aoff, poff = xoff + m * k, aoff + rows * rows, poff + slices * rows * rows
+    assert 0 < len(names) < LARS_NO_TENSOR, "the block map names a tensor in 16 bits"
+    assert max(xoff, poff) < 2 ** 31, "the tables hold int32 offsets"
+    tab = lambda rows, w: np.array(rows, dtype=np.int32).reshape(-1, w)  # noqa: E731
+    return MuonPlan(tuple(names), tab(tensors, 12), np.array(chunks, dtype=np.int32), block_map, cls, tab(tiles, 4),
+                    tab(gram, 4), tab(tri, 4), tab(poly, 4), xoff, aoff, poff, n)
+
+
+def muon_update(flat, mom, grad, lr_t, momentum, decay, plan: MuonPlan, lr_ratio=1.0, nesterov=True, ns_steps=5,
+                only=None) -> list:
+    """The Muon reference, in place.  For every tensor ``T`` of the plan (``only``: just those
+    names; the others' weights are left alone, their momentum still moves), as ``W[m][n]``:
+    ``mom = fma(mu, mom, g)`` in fp32 with ``mu = float32(momentum)``, ``u = fma(mu, mom, g)``
+    (``nesterov``) or ``mom``, ``O = newton_schulz(u, ns_steps, emulate=True)`` and, in float64
+    rounded once, ``w = w (1 - lr_t r decay[0]) - lr_t r sqrt(max(1, m / n)) O``.  Every other
+    element takes :func:`lars_update`'s rule at trust 1 (``d = g + decay[c] w``, ``mom = momentum
+    mom + d``, ``w -= lr_t mom``).  ``mom`` is required.  Returns ``||u||_F`` per Muon tensor."""
+    n = plan.n
+    w, g = flat[:n].double(), grad[:n].double()
+    d = momentum * mom[:n].double() + g + decay_vector(plan.cls, n, decay) * w
+    new_m, new_w = d.to(mom.dtype), (w - lr_t * d).to(flat.dtype)
+    norms = []
+    for name, (off, m, k, *_) in zip(plan.names, plan.tensors.tolist()):
+        sl = slice(off, off + m * k)
+        new_m[sl] = fma32(momentum, mom[sl], grad[sl])
+        u = fma32(momentum, new_m[sl], grad[sl]) if nesterov else new_m[sl]
+        norms.append(float(torch.linalg.vector_norm(u.double())))
+        new_w[sl] = flat[sl]
+        if only is None or name in only:
+            o = newton_schulz(u.view(m, k), ns_steps, emulate=True).reshape(-1)
+            step = lr_t * lr_ratio
+            new_w[sl] = (w[sl] * (1.0 - step * float(decay[0])) - step * math.sqrt(max(1.0, m / k)) * o).to(flat.dtype)
+    mom[:n], flat[:n] = new_m, new_w
+    return norms
+
+
 CLIP_EPS = 1e-6  # torch.nn.utils.clip_grad_norm_'s constant
 
 
@@ -332,6 +490,10 @@ class OptSpec:
     # optimizer="lars": the trust coefficient, and a constant added to the trust ratio's denominator
     lars_eta: float = 0.001
     lars_eps: float = 0.0
+    # optimizer="muon": the Muon tensors' lr over the schedule's, Nesterov momentum, Newton-Schulz iterations
+    muon_lr_ratio: float = 1.0
+    muon_nesterov: bool = True
+    muon_ns_steps: int = 5
 
     def __post_init__(self):
         check_group_decay("norm_weight_decay", self.norm_weight_decay)
@@ -339,6 +501,7 @@ class OptSpec:
         if self.optimizer not in OPTIMIZERS:
             raise ValueError(f"unknown optimizer {self.optimizer!r} (choose from {OPTIMIZERS})")
         check_lars(self.lars_eta, self.lars_eps)
+        check_muon(self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps)
         if self.lr_schedule not in SCHEDULES:
             raise ValueError(f"unknown lr_schedule {self.lr_schedule!r} (choose from {SCHEDULES})")
         if self.lr_warmup_steps < 0 or self.lr_decay_steps < 0:
@@ -373,14 +536,19 @@ class OptSpec:
         return self.optimizer == "lars"
 
     @property
+    def muon(self) -> bool:
+        return self.optimizer == "muon"
+
+    @property
     def scheduled(self) -> bool:
         return self.lr_schedule != "constant" or self.lr_warmup_steps > 0
 
     @property
     def mapped(self) -> bool:
         """The update reads the class map: decay groups on, or LARS (whose exclusion list the
-        classes are), whether or not a class decay is set."""
-        return self.grouped or self.lars
+        classes are) or Muon (whose other elements follow the grouped rule), whether or not a class
+        decay is set."""
+        return self.grouped or self.lars or self.muon
 
     @property
     def grouped(self) -> bool:
@@ -399,8 +567,8 @@ class OptSpec:
         grouped trainer always runs a step-counter rule (a grouped SGD trainer at a fixed lr runs
         ``RULE_SGD_LR`` with no table, which reads the scalar lr), so it has an ``opt_step``, and
         the plain rule's kernels and launches are what they were before groups existed.  Nor is a
-        LARS trainer ever plain."""
-        return not self.adamw and not self.scheduled and not self.grouped and not self.lars
+        LARS or a Muon trainer ever plain."""
+        return not self.adamw and not self.scheduled and not self.grouped and not self.lars and not self.muon
 
     @property
     def rule(self) -> int:
@@ -431,7 +599,12 @@ class OptSpec:
         """One reference update of 0-based ``step``, in place (the CPU trainers' optimizer).
         ``decay``: the per-element weight decay of a grouped spec (:func:`decay_vector`).
         ``plan``: the :func:`lars_plan` of a LARS spec, which takes the class decays from
-        :meth:`decays` and returns :func:`lars_update`'s ``(wn, gn, trust)`` rows."""
+        :meth:`decays` and returns :func:`lars_update`'s ``(wn, gn, trust)`` rows; or the
+        :func:`muon_plan` of a Muon spec, which returns :func:`muon_update`'s norms."""
+        if self.muon:
+            assert plan is not None, "a Muon spec updates with its plan"
+            return muon_update(flat, mom, grad, self.lr_at(step), self.momentum, self.decays(), plan,
+                               self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps)
         if self.lars:
             assert plan is not None, "a LARS spec updates with its plan"
             return lars_update(flat, mom, grad, self.lr_at(step), self.momentum, self.decays(), plan,
@@ -460,6 +633,9 @@ class OptSpec:
             d["bias_weight_decay"] = self.bias_weight_decay
         if self.lars:
             d.update(lars_eta=self.lars_eta, lars_eps=self.lars_eps)
+        if self.muon:
+            d.update(muon_lr_ratio=self.muon_lr_ratio, muon_nesterov=bool(self.muon_nesterov),
+                     muon_ns_steps=int(self.muon_ns_steps))
         return d
 
 
@@ -605,6 +781,105 @@ def sgd_flat_lars(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor | None, st
     N.call("sl_sgd_flat_lars", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), N.ptr(step), N.ptr(lr_tab),
            lr_tab.numel() if lr_tab is not None else 0, float(lr), float(momentum), wd, wd_norm, wd_bias,
            N.ptr(b.cls), N.ptr(b.block_map), N.ptr(b.out), b.tensors.shape[0], N.stream_ptr())
+
+
+MUON_KERNELS = ("sl_muon_chunk", "sl_muon_prep", "sl_muon_gram", "sl_muon_poly", "sl_muon_apply", "sl_sgd_flat_muon")
+
+
+class MuonBuffers:
+    """A :class:`MuonPlan` on a device, uploaded once, with the work buffers the launches share:
+    ``x`` (two bf16 copies of the Muon tensors, the iteration's ping and pong), ``a`` and ``b`` (the
+    Gram matrix and its polynomial), ``ws`` (the fp32 split-K partials of the Gram launch),
+    ``partials`` (fp64 per chunk) and ``norms`` (fp32 ``||u||_F`` per tensor, of the last update)."""
+
+    def __init__(self, plan: MuonPlan, device):
+        assert int(N.lib().sl_muon_chunk()) == MUON_CHUNK, "the kernel library was built with another MUON_CHUNK"
+        up = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+        zeros = lambda k, dt: torch.zeros(k, dtype=dt, device=device)  # noqa: E731
+        self.plan, self.T = plan, len(plan.names)
+        self.tensors_h = np.ascontiguousarray(plan.tensors)  # (the launchers check the shapes on the host copy)
+        self.tensors, self.chunks = up(plan.tensors), up(plan.chunks)
+        self.tiles, self.gram_tiles, self.tri_tiles, self.poly_tiles = (
+            up(t) for t in (plan.tiles, plan.gram_tiles, plan.tri_tiles, plan.poly_tiles))
+        self.block_map, self.cls = up(plan.block_map.view(np.int16)), up(plan.cls)
+        self.x = (zeros(plan.x_elems, torch.bfloat16), zeros(plan.x_elems, torch.bfloat16))
+        self.a, self.b = zeros(plan.a_elems, torch.bfloat16), zeros(plan.a_elems, torch.bfloat16)
+        self.ws = zeros(plan.ws_floats, torch.float32)
+        self.partials = zeros(len(plan.chunks), torch.float64)
+        self.norms = zeros(self.T, torch.float32)
+
+    def _tab(self) -> tuple:
+        return self.tensors_h.ctypes.data, N.ptr(self.tensors), self.T
+
+    def out(self, ns_steps: int) -> torch.Tensor:
+        """The work buffer that holds O after ``ns_steps`` iterations."""
+        return self.x[ns_steps & 1]
+
+    def matrix(self, t: int, ns_steps: int) -> torch.Tensor:
+        """O of tensor ``t`` as its own ``[m][n]``, on the device (a tall one transposed back)."""
+        off, m, k, tall, xoff = self.plan.tensors[t, :5].tolist()
+        o = self.out(ns_steps)[xoff:xoff + m * k]
+        return o.view(k, m).T if tall else o.view(m, k)
+
+
+def _check_muon(g: torch.Tensor, mom: torch.Tensor, b: MuonBuffers) -> None:
+    assert g.is_cuda and g.dtype == torch.float32 and mom.dtype == torch.float32
+    assert g.is_contiguous() and mom.is_contiguous() and g.numel() == mom.numel()
+    assert g.numel() == b.plan.n, "the plan was made for a vector of another length"  # (every chunk is inside it)
+    assert b.tensors.device == g.device
+
+
+def muon_prep(g: torch.Tensor, mom: torch.Tensor, b: MuonBuffers, momentum: float, nesterov: bool = True) -> None:
+    """The Muon tensors' ``mom = fma(mu, mom, g)``, their ``||u||_F`` into ``b.norms`` and their
+    scaled bf16 ``X0`` into ``b.x[0]`` (muon_mom_kernel, muon_x0_kernel)."""
+    _check_muon(g, mom, b)
+    N.call("sl_muon_prep", N.ptr(g), N.ptr(mom), N.ptr(b.chunks), b.chunks.numel(), float(momentum), int(bool(nesterov)),
+           N.ptr(b.partials), *b._tab(), N.ptr(b.tiles), b.tiles.shape[0], N.ptr(b.x[0]), N.ptr(b.norms),
+           N.stream_ptr())
+
+
+def muon_gram(b: MuonBuffers, k: int) -> None:
+    """``b.a = bf16(X X^T)`` of iteration ``k``'s X, ``b.x[k & 1]`` (muon_gram_kernel, muon_fold_kernel)."""
+    N.call("sl_muon_gram", N.ptr(b.x[k & 1]), *b._tab(), N.ptr(b.gram_tiles), b.gram_tiles.shape[0], N.ptr(b.ws),
+           N.ptr(b.tri_tiles), b.tri_tiles.shape[0], N.ptr(b.a), N.stream_ptr())
+
+
+def muon_poly(b: MuonBuffers) -> None:
+    """``b.b = bf16(b A + c A A)`` (muon_poly_kernel)."""
+    N.call("sl_muon_poly", N.ptr(b.a), *b._tab(), N.ptr(b.poly_tiles), b.poly_tiles.shape[0], N.ptr(b.b),
+           N.stream_ptr())
+
+
+def muon_apply(b: MuonBuffers, k: int) -> None:
+    """``b.x[(k + 1) & 1] = bf16(a X + B X)`` of iteration ``k``'s X (muon_apply_kernel)."""
+    N.call("sl_muon_apply", N.ptr(b.x[k & 1]), N.ptr(b.b), *b._tab(), N.ptr(b.tiles), b.tiles.shape[0],
+           N.ptr(b.x[(k + 1) & 1]), N.stream_ptr())
+
+
+def muon_orthogonalize(g: torch.Tensor, mom: torch.Tensor, b: MuonBuffers, momentum: float, nesterov: bool = True,
+                       ns_steps: int = 5) -> None:
+    """Prep and ``ns_steps`` x (gram, poly, apply): ``b.out(ns_steps)`` then holds every O."""
+    muon_prep(g, mom, b, momentum, nesterov)
+    for k in range(int(ns_steps)):
+        muon_gram(b, k)
+        muon_poly(b)
+        muon_apply(b, k)
+
+
+def sgd_flat_muon(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor, step: torch.Tensor,
+                  lr_tab: torch.Tensor | None, b: MuonBuffers, decays, lr: float = 0.0, momentum: float = 0.0,
+                  lr_ratio: float = 1.0, ns_steps: int = 5, shadow: torch.Tensor | None = None) -> None:
+    """The Muon update launch (muon_update_kernel): the blocks ``b.block_map`` gives to a Muon
+    tensor take ``w = w (1 - lr r wd) - lr r s_T O`` with O from ``b.out(ns_steps)``; every other
+    element is :func:`sgd_flat_lr_groups`'s, bit for bit.  The caller advances ``step``."""
+    _check_flat(w, g, shadow)
+    _check_muon(g, mom, b)
+    assert step.dtype == torch.int32 and (lr_tab is None or lr_tab.dtype == torch.float32)
+    wd, wd_norm, wd_bias = (float(d) for d in decays)
+    N.call("sl_sgd_flat_muon", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), N.ptr(step), N.ptr(lr_tab),
+           lr_tab.numel() if lr_tab is not None else 0, float(lr), float(momentum), wd, wd_norm, wd_bias, 1.0,
+           float(lr_ratio), N.ptr(b.cls), N.ptr(b.block_map), *b._tab(), N.ptr(b.x[0]), N.ptr(b.x[1]), int(ns_steps),
+           N.stream_ptr())
 
 
 def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:

@@ -174,6 +174,8 @@ class Worker:
             kw.update(classes=c.n_classes)
         if c.optimizer == "lars":
             kw.update(lars_eta=c.lars_eta, lars_eps=c.lars_eps)
+        if c.optimizer == "muon":
+            kw.update(muon_lr_ratio=c.muon_lr_ratio, muon_nesterov=c.muon_nesterov, muon_ns_steps=c.muon_ns_steps)
         kw.update(c.decay_groups)  # norm_weight_decay / bias_weight_decay, where set
         if c.norm != "batch":  # (a stem or input size it does not serve is refused by the trainer)
             kw.update(norm=c.norm, norm_groups=c.norm_groups)
@@ -189,6 +191,9 @@ class Worker:
                           **{f"{k}_elements": n for k, n in zip(DECAY_CLASSES, counts)})
         if c.optimizer == "lars":
             self.log.info("lars", eta=c.lars_eta, eps=c.lars_eps, tensors=len(self.trainer.lars_plan.names))
+        if c.optimizer == "muon":
+            self.log.info("muon", lr_ratio=c.muon_lr_ratio, nesterov=bool(c.muon_nesterov), ns_steps=c.muon_ns_steps,
+                          tensors=len(self.trainer.muon_plan.names))
         if c.ema_decay != 0:
             self.log.info("ema",decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
         if self.cfg.sync in ("gossip", "ps"):
