@@ -274,6 +274,13 @@ int sl_mlp_opt_xgmi_groups(int rule, float* w, float* mom, float* v, float lr, f
                            int lr_n, float b1, float b2, float omb1, float omb2, float lnb1, float lnb2, float eps,
                            float wd_bias, hipStream_t stream);
 
+// weight_std.hip: grouped wave-per-filter weight standardization of the ResNet trainers (weight_std=True)
+int sl_wstd_fwd(const float* w, uint16_t* shadow, float* stats_out, long total, const int* tensors_h,
+                const int* tensors, int T, const int* work_h, const int* work, int n_work, double eps,
+                hipStream_t stream);
+int sl_wstd_bwd(const float* w, float* grad, long total, const int* tensors_h, const int* tensors, int T,
+                const int* work_h, const int* work, int n_work, double eps, hipStream_t stream);
+
 // xgmi.hip
 int sl_xgmi_header_bytes();
 long sl_xgmi_buffer_bytes(long slot_bytes);

@@ -61,6 +61,8 @@ class Config:
     norm: str = "batch"                # resnet18: batch (BatchNorm) | group (GroupNorm: no running statistics, the
                                        # flat vector is the whole model; cifar stem, inputs up to 32 x 32)
     norm_groups: int = 32              # norm=group: groups per layer, one of 8, 16, 32, 64
+    weight_std: bool = False           # resnet18: every convolution reads its filters standardized over their fan-in
+                                       # (the published partner of norm=group; works with either norm)
     batch: int = 1024
     lr: float = 0.05
     momentum: float = 0.9
@@ -201,6 +203,8 @@ class Config:
             raise ValueError("norm_weight_decay: the mlp model has no normalisation layer (model='resnet18')")
 
     def _validate_norm(self) -> None:
+        if self.weight_std and self.model in ("mlp", "simulate"):
+            raise ValueError(f"weight_std: the {self.model} model has no convolution filter (model='resnet18')")
         if self.norm not in ("batch", "group"):
             raise ValueError(f"norm must be 'batch' or 'group', got {self.norm!r}")
         if self.norm == "batch":

@@ -36,6 +36,7 @@ CIFAR_STD = (0.2470, 0.2435, 0.2616)
 STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))
 NORMS = ("batch", "group")
 NORM_GROUPS = (8, 16, 32, 64)  # with 64..512 channels: 1..64 channels per group
+WS_EPS = 1e-6  # weight standardization: added to a filter's variance (timm's StdConv2d default); not a knob
 
 
 def check_norm(norm: str, groups, stem: str, in_hw: int) -> int:
@@ -215,8 +216,23 @@ def running_stats(spec: ResNetSpec, device="cpu") -> dict:
     return {b.name: (torch.zeros(b.c, device=device), torch.ones(b.c, device=device)) for b in spec.bns()}
 
 
-def conv_weight_nchw(flat: torch.Tensor, c: ConvSpec) -> torch.Tensor:
+def standardize_weight(w: torch.Tensor, cin_real: int | None = None) -> torch.Tensor:
+    """Weight standardization (Qiao et al. 2019) of a conv bank ``w`` [cout, k, k, cin], the definition
+    the kernels of csrc/kernels/weight_std.hip are tested against: every filter (row) is re-centred and
+    re-scaled over its fan-in, ``(w - mean) / sqrt(var + WS_EPS)`` with the biased variance, over the
+    first ``cin_real`` input channels (the stem's 3 of 8); the padding channels come out exactly 0.
+    No gain: the norm layer that follows every conv has one.  Plain torch, differentiable, in ``w``'s
+    dtype."""
+    real = w[..., :cin_real or w.shape[-1]]
+    mu = real.mean(dim=(1, 2, 3), keepdim=True)
+    var = ((real - mu) ** 2).mean(dim=(1, 2, 3), keepdim=True)
+    return F.pad((real - mu) / torch.sqrt(var + WS_EPS), (0, w.shape[-1] - real.shape[-1]))
+
+
+def conv_weight_nchw(flat: torch.Tensor, c: ConvSpec, weight_std: bool = False) -> torch.Tensor:
     w = flat[c.off:c.off + c.numel].view(c.cout, c.k, c.k, c.cin)
+    if weight_std:
+        w = standardize_weight(w, c.cin_real)
     return w[..., :c.cin_real].permute(0, 3, 1, 2)
 
 
@@ -230,10 +246,11 @@ def normalize_input(x_u8: torch.Tensor) -> torch.Tensor:
 
 def ref_forward(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, training: bool = True,
                 running: dict | None = None, momentum: float = 0.1, eps: float = 1e-5, norm: str = "batch",
-                groups: int = 32) -> torch.Tensor:
+                groups: int = 32, weight_std: bool = False) -> torch.Tensor:
     """fp32 NCHW torch forward of exactly the network the HIP engine runs.  ``norm="group"``: every
     normalisation is ``F.group_norm`` over ``groups`` groups (no running statistics, and
-    ``training`` makes no difference)."""
+    ``training`` makes no difference).  ``weight_std``: every convolution uses
+    :func:`standardize_weight` of its filters (``fc.weight`` is left as it is)."""
     def bn(x, b: BNSpec):
         if norm == "group":
             return F.group_norm(x, groups, flat[b.g_off:b.g_off + b.c], flat[b.b_off:b.b_off + b.c], eps)
@@ -242,7 +259,7 @@ def ref_forward(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, traini
                             training=training or rm is None, momentum=momentum, eps=eps)
 
     def conv(x, c: ConvSpec):
-        return F.conv2d(x, conv_weight_nchw(flat, c), stride=c.stride, padding=c.pad)
+        return F.conv2d(x, conv_weight_nchw(flat, c, weight_std), stride=c.stride, padding=c.pad)
 
     x = normalize_input(x_u8)
     x = F.relu(bn(conv(x, spec.stem_conv), spec.stem_bn))
@@ -260,13 +277,14 @@ def ref_forward(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, traini
 
 def ref_grads(spec: ResNetSpec, flat: torch.Tensor, x_u8: torch.Tensor, y: torch.Tensor, grad_scale: float,
               running: dict | None = None, targets: torch.Tensor | None = None, norm: str = "batch",
-              groups: int = 32):
+              groups: int = 32, weight_std: bool = False):
     """(loss_sum, correct, grad_flat) with d(loss_i)/dlogits scaled by grad_scale.  ``x_u8`` is in
     pixel units (u8, or float after a mix); ``targets`` ([B, classes] probabilities) replaces the
-    one-hot ``y`` in the loss, and ``correct`` stays the argmax against ``y``.  ``norm`` / ``groups``
-    as in :func:`ref_forward`."""
+    one-hot ``y`` in the loss, and ``correct`` stays the argmax against ``y``.  ``norm`` / ``groups`` /
+    ``weight_std`` as in :func:`ref_forward`; under ``weight_std`` the gradient is with respect to the
+    raw weights, through the standardization."""
     w = flat.detach().clone().float().requires_grad_(True)
-    logits = ref_forward(spec, w, x_u8, True, running, norm=norm, groups=groups)
+    logits = ref_forward(spec, w, x_u8, True, running, norm=norm, groups=groups, weight_std=weight_std)
     losses = F.cross_entropy(logits, y.long() if targets is None else targets.to(logits.dtype), reduction="none")
     (losses.sum() * grad_scale).backward()
     correct = (logits.argmax(1) == y.long()).float().sum()
@@ -283,10 +301,15 @@ class ResNetModel:
     GroupNorm's, at the same offsets: there are no running statistics (``running_stats()`` is
     empty), so the flat vector is the whole model.  The flat size is the same under both kinds, so
     a checkpoint of one loads into a trainer of the other without a size error; ``model_name``
-    (in the checkpoint's metadata) tells them apart."""
+    (in the checkpoint's metadata) tells them apart.
+
+    With ``weight_std`` every convolution reads its filters standardized (:func:`standardize_weight`);
+    the flat vector, the optimizer and the checkpoint hold the raw weights, and ``model_name`` gains
+    ``-ws``."""
 
     norm = "batch"
     norm_groups = 0
+    weight_std = False
     # optimizer="lars" (TrainerState): conv / fc weights adapted, norms and fc.bias not; and optimizer="muon": the
     # conv weights but the stem's orthogonalised
     lars_capable = True
@@ -298,7 +321,7 @@ class ResNetModel:
     @property
     def model_name(self) -> str:
         gn = f"-gn{self.norm_groups}" if self.norm == "group" else ""
-        return f"resnet18-{self.spec.stem}{gn}"
+        return f"resnet18-{self.spec.stem}{gn}{'-ws' if self.weight_std else ''}"
 
     def layout(self):
         return spec_layout(self.spec)
@@ -336,7 +359,7 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
                  flat: torch.Tensor | None = None, in_hw: int | None = None, augment: str = "none",
                  augment_pad: int = 4, shuffle: bool = False, label_smoothing: float = 0.0, mixup_alpha: float = 0.0,
                  cutmix_alpha: float = 0.0, accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32,
-                 **opt):
+                 weight_std: bool = False, **opt):
         from ..data import augment as A
 
         if isinstance(classes, bool) or int(classes) != classes or not 1 <= classes <= 256:
@@ -358,6 +381,9 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
                        weight_decay, world_size, accum_steps, opt)
         self.running = running_stats(self.spec) if norm == "batch" else {}
         self._norm_kw = dict(norm=norm, groups=self.norm_groups) if norm == "group" else {}
+        self.weight_std = bool(weight_std)
+        if self.weight_std:
+            self._norm_kw["weight_std"] = True
 
     def running_stats(self) -> dict:
         return self.running

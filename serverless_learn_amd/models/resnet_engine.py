@@ -39,6 +39,12 @@ csrc/kernels/groupnorm.hip, through a forward and backward of their own (``_forw
 ReLU and mask in one pass) and one ``gn_bwd`` + ``gn_param_fold`` per layer.  There is no statistics
 arena and there are no running statistics, evaluation runs the training forward, and none of the
 BatchNorm fusions above apply; input pipeline, loss, buckets, update, EMA and capture are shared.
+
+With ``weight_std=True`` the conv slices of the bf16 shadow hold the standardized filters
+(csrc/kernels/weight_std.hip): one ``wstd_fwd`` launch after every launch that rewrites the shadow
+from the parameters, and one ``wstd_bwd`` launch per step that takes the aggregated gradient from
+dL/dwhat back to dL/dw, ahead of the clip and the update.  The flat vector, the optimizer, the EMA
+and every exchange see the raw weights and their true gradient.
 """
 from __future__ import annotations
 
@@ -47,8 +53,8 @@ import os
 import torch
 
 from ..utils.graphs import GraphedStep
-from .resnet import (CIFAR_MEAN, CIFAR_STD, BlockSpec, BNSpec, ConvSpec, ResNetModel, check_norm, init_params,
-                     resnet18_spec)
+from .resnet import (CIFAR_MEAN, CIFAR_STD, WS_EPS, BlockSpec, BNSpec, ConvSpec, ResNetModel, check_norm,
+                     init_params, resnet18_spec)
 from .trainer_state import StepStats, TrainerState
 
 LOGIT_LD = 16  # dlogits row stride up to 16 classes (classes padded for 16-B gathers); above: ops.cnn.logit_ld
@@ -112,7 +118,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
                  label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
-                 accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32, **opt):
+                 accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32, weight_std: bool = False, **opt):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
@@ -268,6 +274,10 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                  for c in self.conv.values() if c.spec.name != "stem"]
         items.append((self.fc_w, self.fc_wt, classes, 1, 512, self.logit_ld))
         self.wt = K.WeightTransposer(items, dev)
+        # weight_std: the plan of the two grouped launches over the conv banks (None: nothing is
+        # allocated and no launch is added)
+        self.weight_std = bool(weight_std)
+        self.wstd = K.wstd_plan(spec.convs(), dev) if self.weight_std else None
         self.refresh_shadows()
         self.stats()  # load torch's reduction kernel now, not inside the first logged chunk (as mlp.py)
 
@@ -283,7 +293,20 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
     # ------------------------------------------------------------------
     def refresh_shadows(self) -> None:
         self.O.to_bf16(self.params, self.shadow)
+        self._standardize()
         self.wt()
+
+    def _standardize(self) -> None:
+        """weight_std: the conv slices of the shadow, just written as bf16(w), become bf16(what)."""
+        if self.wstd is not None:
+            self.K.wstd_fwd(self.params, self.shadow, self.wstd, eps=WS_EPS)
+
+    def _unstandardize_grad(self) -> None:
+        """weight_std: the conv slices of the gradient from dL/dwhat (what conv_wgrad leaves) to dL/dw.
+        The map is linear in the gradient and depends only on the parameters, which are the same for
+        every micro-batch and on every all-reduce replica, so it runs once, on the aggregated sum."""
+        if self.wstd is not None:
+            self.K.wstd_bwd(self.params, self.grad, self.wstd, eps=WS_EPS)
 
     def load_shard(self, x_u8: torch.Tensor, y_u8: torch.Tensor) -> None:
         """The resident shard.  With the input pipeline on, the epoch is cursor // (N // batch): a
@@ -620,11 +643,13 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         if self.allreduce is not None:
             self.allreduce(self.grad)
         self.phases.mark("exchange")
+        self._unstandardize_grad()
         if self.opt.clips:  # on the aggregated gradient, before the unchanged update rule
             self.O.clip_grad_norm_flat(self.grad, self.opt.clip_grad_norm, self.clip_partials, self.clip_norm)
         self._update()
         if self.ema is not None:  # on the parameters just written; the launch advances ema_step itself
             self.O.ema_flat(self.ema, self.params, self.ema_step, self.ema_ticket, self.ema_tab)
+        self._standardize()
         self.wt()
         self.K.cursor_bump(self.cursor)
         self.phases.mark("update")
@@ -679,6 +704,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.grad.zero_()
         self.forward(train=True)
         self.backward()
+        self._unstandardize_grad()
         return self.grad
 
     def stats(self) -> StepStats:

@@ -497,6 +497,70 @@ def gn_param_fold(ws, n: int, grad_gamma, grad_beta):
     N.call("sl_gn_param_fold", p(ws), int(n), c, _f32(grad_gamma), _f32(grad_beta), N.stream_ptr())
 
 
+# ---- weight standardization, one wave per filter row (csrc/kernels/weight_std.hip) ----
+WSTD_FIELDS = 8     # ints per bank of the tensor table (weight_std.hip WsTensor)
+WSTD_ROWS = 4       # filter rows per workgroup, one per wave
+WSTD_MAX_N = 4608   # the longest row the kernels hold in registers (18 rounds of 64 float4)
+
+
+class WstdPlan:
+    """:func:`wstd_plan`'s result: the tensor table int32 ``[T][8]`` = (offset, rows, n, cin, cin_real,
+    first row, 0, 0) and the work table int32 ``[n_work][2]`` = (bank, first row), each on the host
+    (the launchers check the host copy) and on the device.  ``rows``: filter rows of all banks, the
+    length of the forward's optional ``stats_out`` (``[rows][2]``, in plan order)."""
+
+    def __init__(self, tensors, work, device):
+        import numpy as np
+
+        self.tensors_h, self.work_h = np.ascontiguousarray(tensors), np.ascontiguousarray(work)
+        self.tensors, self.work = torch.from_numpy(self.tensors_h).to(device), torch.from_numpy(self.work_h).to(device)
+        self.T, self.n_work, self.rows = len(tensors), len(work), int(self.tensors_h[:, 1].sum())
+
+    def _tab(self) -> tuple:
+        return self.tensors_h.ctypes.data, p(self.tensors), self.T, self.work_h.ctypes.data, p(self.work), self.n_work
+
+
+def wstd_plan(convs, device="cuda") -> WstdPlan:
+    """How the two weight-standardization launches see the conv banks ``convs`` (``ConvSpec``s: off,
+    cout, k, cin, cin_real) of a flat vector: one workgroup per :data:`WSTD_ROWS` rows of a bank, the
+    banks with the longest rows first, so the grid's tail is the short rows.  Shapes are not judged
+    here: the launchers refuse what the kernels do not serve."""
+    import numpy as np
+
+    convs = list(convs)
+    tensors = np.zeros((len(convs), WSTD_FIELDS), dtype=np.int32)
+    row0 = 0
+    for i, c in enumerate(convs):
+        tensors[i, :6] = (c.off, c.cout, c.k * c.k * c.cin, c.cin, c.cin_real, row0)
+        row0 += c.cout
+    order = sorted(range(len(convs)), key=lambda i: -int(tensors[i, 2]))  # (stable: plan order within a length)
+    work = [(i, r) for i in order for r in range(0, int(tensors[i, 1]), WSTD_ROWS)]
+    return WstdPlan(tensors, np.array(work, dtype=np.int32).reshape(-1, 2), device)
+
+
+def wstd_fwd(params, shadow, plan: WstdPlan, stats_out=None, eps: float = 1e-6):
+    """Every bank's slice of ``shadow`` (bf16) = the standardized filters of the same slice of ``params``
+    (fp32): per row ``(w - mean) / sqrt(var + eps)`` over the real columns, exactly 0 on padding
+    columns (models/resnet.py ``standardize_weight``).  Nothing outside the banks is written.
+    ``stats_out`` (fp32 ``[plan.rows][2]``) receives each row's (mean, 1 / sqrt(var + eps))."""
+    assert params.dtype == torch.float32 and shadow.dtype == torch.bfloat16 and shadow.numel() == params.numel()
+    assert params.is_contiguous() and shadow.is_contiguous()
+    if stats_out is not None:
+        assert stats_out.dtype == torch.float32 and stats_out.numel() == 2 * plan.rows and stats_out.is_contiguous()
+    N.call("sl_wstd_fwd", p(params), p(shadow), p(stats_out), params.numel(), *plan._tab(), float(eps),
+           N.stream_ptr())
+
+
+def wstd_bwd(params, grad, plan: WstdPlan, eps: float = 1e-6):
+    """Every bank's slice of ``grad`` from ``dL/dwhat`` to ``dL/dw``, in place: per row
+    ``r (G - mean(G) - what mean(G what))`` over the real columns, 0 on padding columns, with the
+    row's statistics rebuilt from ``params``.  The map is linear in ``G``, so it is applied once to a
+    gradient that was summed over micro-batches or replicas of the same ``params``."""
+    assert params.dtype == grad.dtype == torch.float32 and grad.numel() == params.numel()
+    assert params.is_contiguous() and grad.is_contiguous()
+    N.call("sl_wstd_bwd", p(params), p(grad), params.numel(), *plan._tab(), float(eps), N.stream_ptr())
+
+
 def maxpool_fwd(x, y, arg, k=3, s=2, pad=1):
     n, h, w, c = x.shape
     _, oh, ow, _ = y.shape

@@ -179,9 +179,16 @@ class Worker:
         kw.update(c.decay_groups)  # norm_weight_decay / bias_weight_decay, where set
         if c.norm != "batch":  # (a stem or input size it does not serve is refused by the trainer)
             kw.update(norm=c.norm, norm_groups=c.norm_groups)
+        if c.weight_std:  # (Config refuses it for the MLP)
+            kw.update(weight_std=True)
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if c.norm != "batch":
             self.log.info("norm", kind=c.norm, groups=int(c.norm_groups))
+        if c.weight_std:
+            from ..models.resnet import WS_EPS
+
+            banks = list(self.trainer.spec.convs())
+            self.log.info("weight_std", eps=WS_EPS, banks=len(banks), rows=sum(b.cout for b in banks))
         if c.decay_groups:
             from ..ops.optim import DECAY_CLASSES, decay_class_counts
 
