@@ -36,6 +36,9 @@ int sl_input_mix(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_
                  int pad, int flags, unsigned long long seed, const int* table, int modes, uint16_t* y,
                  uint8_t* lab_out, int* params_out, int* mix_out, float m0, float m1, float m2, float s0, float s1,
                  float s2, hipStream_t stream);
+int sl_input_ta(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_records, int batch, int H, int W,
+                int pad, int flags, unsigned long long seed, const int* table, uint8_t* ta_x, uint8_t* ta_lab,
+                int* params_out, int* ta_out, int force, hipStream_t stream);
 int sl_cursor_bump(int* cursor, hipStream_t stream);
 int sl_bn_finalize(const float* stats, const float* gamma, const float* beta, float* coef, float* run_mean,
                    float* run_var, int C, float count, float eps, float momentum, hipStream_t stream);

@@ -94,6 +94,8 @@ class Config:
     augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip, data/augment.py)
     augment_pad: int = 4               # crop-flip: black pixels of padding around the image the crop is taken from
     shuffle: bool = False              # resnet18: draw each epoch's records through a fresh permutation of the shard
+    auto_augment: str = "none"         # resnet18: none | trivial-wide (TrivialAugment Wide: one random operation per
+                                       # image after crop / flip, data/augment.py; images up to 64 x 64)
     label_smoothing: float = 0.0       # resnet18: smooth the training targets by this much (0 <= eps < 1)
     mixup_alpha: float = 0.0           # resnet18: mixup with lambda ~ Beta(alpha, alpha) per batch (0 = off)
     cutmix_alpha: float = 0.0          # resnet18: CutMix likewise; with both on, one of the two per batch
@@ -170,6 +172,12 @@ class Config:
         if (self.augment, self.augment_pad, self.shuffle) != ("none", 4, False) and self.model in ("mlp", "simulate"):
             # the MLP kernels read X from bricks tiled once per shard: a per-sample gather would undo that
             raise ValueError(f"augment / shuffle: the {self.model} model has no input pipeline (model='resnet18')")
+        if self.auto_augment != "none":
+            from .data.augment import check_ta
+
+            check_ta(self.auto_augment)  # (an image too large for the kernel is refused by the trainer)
+            if self.model in ("mlp", "simulate"):
+                raise ValueError(f"auto_augment: the {self.model} model has no input pipeline (model='resnet18')")
         if (self.label_smoothing, self.mixup_alpha, self.cutmix_alpha) != (0, 0, 0):  # NaN included
             from .data.augment import check_mix
 

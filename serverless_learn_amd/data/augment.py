@@ -33,8 +33,16 @@ the batch within it.  All arithmetic is on unsigned 32-bit integers.
   weighs the pasted area over ``H W``.  :func:`soft_targets` adds label smoothing:
   ``q = (1 - eps)(wa [c = la] + wb [c = lb]) + eps / ncls``.
 
+* **TrivialAugment Wide** (``auto_augment="trivial-wide"``; after crop / flip, before the mix, whose
+  partner is then the partner after its own operation).  ``T = philox4x32_10(t, 0, j, 4; seed)``:
+  sample ``j`` gets the one operation ``op = T.x % 14`` of torchvision's ``TrivialAugmentWide`` list at
+  strength ``bin = T.y % 31`` (``m = bin / 30``) and sign ``neg = T.z & 1``.  Every constant that
+  involves a float is rounded once on the host into :func:`ta_table`; :func:`ta_apply` and
+  ``input_ta_kernel`` (csrc/kernels/input_ta.hip) read the same integers and do integer arithmetic
+  only, so they agree bit for bit.  The operations are written out at :func:`ta_apply`.
+
 The shard generator uses Philox's fourth counter word 0 (data/device_synth.py); the streams here
-use 1, 2 and 3, so they never collide with it under one seed.
+use 1, 2, 3 and 4, so they never collide with it under one seed.
 """
 from __future__ import annotations
 
@@ -47,6 +55,12 @@ from .device_synth import MASK, philox4x32_10
 
 AUGMENTS = ("none", "crop-flip")
 STREAM_SHUFFLE, STREAM_CROP, STREAM_MIX = 1, 2, 3
+STREAM_TA = 4
+AUTO_AUGMENTS = ("none", "trivial-wide")
+TA_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+          "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")  # torchvision's order
+TA_BINS = 31
+TA_MAX_PIXELS = 4096  # one workgroup keeps one image in LDS, a packed word per pixel
 MIX_L = 4096  # entries of a mix table (the table index is the top 12 bits of a Philox word)
 MODE_MIXUP, MODE_CUTMIX = 1, 2  # column 3 of mix_params; bits of sl_input_mix's modes
 FLAG_SHUFFLE, FLAG_CROP_FLIP = 1, 2  # sl_input_aug's flags
@@ -290,3 +304,130 @@ def soft_targets(labels: np.ndarray, mix: np.ndarray | None, eps: float, ncls: i
         np.add.at(q, (rows, la), 1.0 - wb)
         np.add.at(q, (rows, la[mix[:, 0]]), wb)
     return (1.0 - eps) * q + eps / ncls
+
+
+# ---- TrivialAugment Wide ----
+def check_ta(auto_augment: str, in_hw: int | None = None) -> None:
+    """Refuse what no trainer implements (Config and both trainers call this)."""
+    if auto_augment not in AUTO_AUGMENTS:
+        raise ValueError(f"unknown auto_augment {auto_augment!r} (choose from {AUTO_AUGMENTS})")
+    if auto_augment != "none" and in_hw is not None and in_hw * in_hw > TA_MAX_PIXELS:
+        raise ValueError(f"auto_augment: an image of {in_hw} x {in_hw} pixels does not fit the kernel's workgroup "
+                         f"(at most {TA_MAX_PIXELS} pixels)")
+
+
+@functools.lru_cache(maxsize=None)
+def ta_table() -> np.ndarray:
+    """int32 [14, 31, 2, 8] (op, bin, neg): the constants of every operation at every strength,
+    computed in float64 and rounded once.  Ops 1-5 hold (A, B, Cx, D, E, Cy) of the inverse map in
+    Q16 (the translations doubled, as the coordinates are); ops 6-9 the blend factor F in column 0;
+    Posterize its bit mask; Solarize its threshold; the others nothing."""
+    tab = np.zeros((len(TA_OPS), TA_BINS, 2, 8), np.int64)
+    q = 65536
+    for b in range(TA_BINS):
+        m = b / (TA_BINS - 1)
+        for neg in (0, 1):
+            sg = -1 if neg else 1
+            sh = sg * int(np.rint(0.99 * m * q))
+            tr = sg * int(np.rint(32.0 * m)) * 2 * q
+            th = math.radians(sg * 135.0 * m)
+            c, s = int(np.rint(math.cos(th) * q)), int(np.rint(math.sin(th) * q))
+            tab[1, b, neg, :6] = (q, sh, 0, 0, q, 0)    # source x = x + s y about the centre
+            tab[2, b, neg, :6] = (q, 0, 0, sh, q, 0)    # source y = y + s x
+            tab[3, b, neg, :6] = (q, 0, -tr, 0, q, 0)   # the image moves right by k: source x = x - k
+            tab[4, b, neg, :6] = (q, 0, 0, 0, q, -tr)
+            tab[5, b, neg, :6] = (c, -s, 0, s, c, 0)    # counter-clockwise by theta, as np.rot90 turns
+            tab[6:10, b, neg, 0] = 256 + sg * int(np.rint(0.99 * 256.0 * m))
+            tab[10, b, neg, 0] = (0xFF << int(np.rint(6.0 * m))) & 0xFF  # keeps 8 - rint(6 m) high bits
+            tab[11, b, neg, 0] = 255 - int(np.rint(255.0 * m))
+    tab = tab.astype(np.int32)
+    tab.setflags(write=False)
+    return tab
+
+
+def ta_params(seed: int, t: int, batch: int) -> np.ndarray:
+    """int32 [batch, 4] of (op, bin, neg, 0) at cursor ``t``."""
+    r = philox4x32_10(t, 0, np.arange(batch, dtype=np.uint64), STREAM_TA, *_keys(seed))
+    out = np.zeros((batch, 4), np.int32)
+    out[:, 0] = r[0] % np.uint64(len(TA_OPS))
+    out[:, 1] = r[1] % np.uint64(TA_BINS)
+    out[:, 2] = r[2] & np.uint64(1)
+    return out
+
+
+def _grey(a: np.ndarray) -> np.ndarray:
+    return (77 * a[..., 0] + 150 * a[..., 1] + 29 * a[..., 2] + 128) >> 8
+
+
+def _ta_one(a: np.ndarray, op: int, e: np.ndarray) -> np.ndarray:
+    """One image ``a`` (int64 [H, W, 3], values 0..255) under operation ``op`` with table row ``e``."""
+    hh, ww, _ = a.shape
+    if op == 0:
+        return a
+    if op <= 5:  # nearest-neighbour inverse affine map about the centre, black outside
+        v, u = np.meshgrid(2 * np.arange(hh) - (hh - 1), 2 * np.arange(ww) - (ww - 1), indexing="ij")
+        sx = (e[0] * u + e[1] * v + e[2] + (ww - 1) * 65536 + 65536) >> 17
+        sy = (e[3] * u + e[4] * v + e[5] + (hh - 1) * 65536 + 65536) >> 17
+        inside = (sx >= 0) & (sx < ww) & (sy >= 0) & (sy < hh)
+        out = a[np.clip(sy, 0, hh - 1), np.clip(sx, 0, ww - 1)]
+        return np.where(inside[..., None], out, 0)
+    if op <= 9:  # blend with a degenerate image d: a at F = 256, d at F = 0, beyond a above 256
+        if op == 6:
+            d = np.zeros_like(a)
+        elif op == 7:
+            d = np.broadcast_to(_grey(a)[..., None], a.shape)
+        elif op == 8:
+            d = np.full_like(a, (int(_grey(a).sum()) + hh * ww // 2) // (hh * ww))
+        else:
+            d = a.copy()
+            if hh > 2 and ww > 2:
+                box = sum(a[dy:hh - 2 + dy, dx:ww - 2 + dx] for dy in range(3) for dx in range(3))
+                d[1:-1, 1:-1] = (box + 4 * a[1:-1, 1:-1] + 6) // 13
+        return np.clip((256 * d + e[0] * (a - d) + 128) >> 8, 0, 255)
+    if op == 10:
+        return a & e[0]
+    if op == 11:
+        return np.where(a < e[0], a, 255 - a)
+    out = a.copy()
+    for c in range(3):
+        ch = a[..., c]
+        if op == 12:
+            lo, hi = int(ch.min()), int(ch.max())
+            if hi != lo:
+                out[..., c] = ((ch - lo) * 510 + (hi - lo)) // (2 * (hi - lo))
+        else:  # PIL's equalize
+            h = np.bincount(ch.reshape(-1), minlength=256)
+            step = (hh * ww - int(h[np.nonzero(h)[0][-1]])) // 255
+            if step:
+                lut = np.minimum(255, (step // 2 + np.cumsum(h) - h) // step)
+                out[..., c] = lut[ch]
+    return out
+
+
+def ta_apply(a_u8: np.ndarray, ta: np.ndarray, table: np.ndarray | None = None) -> np.ndarray:
+    """The u8 [B, H, W, 3] batch after each sample's operation ``ta[j] = (op, bin, neg, 0)``; ``a_u8`` is
+    :func:`apply`'s output.  Integers only.  With ``e = table[op, bin, neg]``:
+
+    * 1-5 ShearX, ShearY, TranslateX, TranslateY, Rotate: with the doubled centred coordinates
+      ``u = 2x - (W-1)``, ``v = 2y - (H-1)``, output pixel ``(y, x)`` reads source
+      ``sx = (A u + B v + Cx + (W-1) 65536 + 65536) >> 17`` and ``sy`` likewise from ``(D, E, Cy)``
+      (floor); black outside.  Shear factor ``+-0.99 m``, translation ``+-rint(32 m)`` pixels, rotation
+      ``+-135 m`` degrees.
+    * 6-9 Brightness, Color, Contrast, Sharpness: ``clamp((256 d + F (a - d) + 128) >> 8, 0, 255)``,
+      ``F = 256 +- rint(0.99 * 256 m)``; ``d`` is 0, the grey ``L = (77 r + 150 g + 29 b + 128) >> 8``, the
+      image mean of ``L`` (``(sum + HW // 2) // HW``), or the 3x3 smooth ``(sum_9 a + 4 a + 6) // 13`` at
+      interior pixels and ``a`` on the border.
+    * 10 Posterize keeps ``8 - rint(6 m)`` high bits; 11 Solarize: ``a < th ? a : 255 - a``,
+      ``th = 255 - rint(255 m)``.
+    * 12 AutoContrast, per channel: ``((a - lo) 510 + (hi - lo)) // (2 (hi - lo))``, unchanged if
+      ``hi == lo``.  13 Equalize, per channel, PIL's rule: ``step = (HW - h[largest occupied level]) //
+      255``; unchanged if 0, else ``lut[v] = min(255, (step // 2 + sum_{w<v} h[w]) // step)``."""
+    a = np.asarray(a_u8)
+    if a.ndim != 4 or a.shape[3] != 3 or a.shape[1] * a.shape[2] > TA_MAX_PIXELS or len(ta) != len(a):
+        raise ValueError(f"ta_apply: a batch [B, H, W, 3] of at most {TA_MAX_PIXELS} pixels per image and one row of "
+                         f"ta per sample, got {a.shape} and {len(ta)} rows")
+    tab = (ta_table() if table is None else np.asarray(table)).astype(np.int64)
+    out = np.empty(a.shape, np.uint8)
+    for j, (op, b, neg, _) in enumerate(np.asarray(ta)):
+        out[j] = _ta_one(a[j].astype(np.int64), int(op), tab[op, b, neg])
+    return out

@@ -359,7 +359,7 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
                  flat: torch.Tensor | None = None, in_hw: int | None = None, augment: str = "none",
                  augment_pad: int = 4, shuffle: bool = False, label_smoothing: float = 0.0, mixup_alpha: float = 0.0,
                  cutmix_alpha: float = 0.0, accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32,
-                 weight_std: bool = False, **opt):
+                 weight_std: bool = False, auto_augment: str = "none", **opt):
         from ..data import augment as A
 
         if isinstance(classes, bool) or int(classes) != classes or not 1 <= classes <= 256:
@@ -368,6 +368,11 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         self.norm, self.norm_groups = norm, check_norm(norm, norm_groups, stem, self.spec.in_hw)
         A.check(augment, augment_pad, self.spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
+        A.check_ta(auto_augment, self.spec.in_hw)
+        # TrivialAugment Wide between crop / flip and the mix (data/augment.py ta_apply); ta_out is the
+        # last batch's (op, bin, neg, 0), None with it off
+        self.auto_augment = auto_augment
+        self.ta_out = None
         # the training input pipeline (data/augment.py), keyed on (seed, cursor, sample) like the
         # GPU engine's; last_aug is the last batch's (record, oy, ox, flip), None with it off
         self.seed, self.augment, self.augment_pad, self.shuffle = seed, augment, augment_pad, bool(shuffle)
@@ -400,10 +405,15 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         from ..data import augment as A
 
         mixes = self.mixup_alpha > 0 or self.cutmix_alpha > 0
-        if self.shuffle or self.augment != "none" or mixes:
+        ta = self.auto_augment != "none"
+        if self.shuffle or self.augment != "none" or mixes or ta:
             self.last_aug = A.batch_params(self.seed, self.cursor, self.x.shape[0], self.batch, self.augment_pad,
                                            self.shuffle, self.augment)
-            xs = torch.from_numpy(A.apply(self.x.cpu().numpy(), self.last_aug, self.augment_pad))
+            xs = A.apply(self.x.cpu().numpy(), self.last_aug, self.augment_pad)
+            if ta:
+                self.ta_out = A.ta_params(self.seed, self.cursor, self.batch)
+                xs = A.ta_apply(xs, self.ta_out)
+            xs = torch.from_numpy(xs)
             ys = self.y[torch.from_numpy(self.last_aug[:, 0].astype(np.int64))]
         else:
             b = self.cursor % self.n_batches

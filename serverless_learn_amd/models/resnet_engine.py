@@ -9,7 +9,7 @@ cursor, like the MLP engine).
 
 Per step:
   forward   input_norm (input_aug with shuffle= / augment= on, input_mix with mixup_alpha= /
-            cutmix_alpha= on: data/augment.py) ->
+            cutmix_alpha= on, input_ta in front of either with auto_augment= on: data/augment.py) ->
             [conv (+BN stats in the epilogue) -> bn_apply with
             the finalize folded in (+residual, ReLU)] x 20 -> avgpool -> fc ->
             softmax-CE (loss, dlogits, dbias; against soft targets with a mix or
@@ -118,7 +118,8 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                  classes: int = 10, flat: torch.Tensor | None = None, bn_momentum: float = 0.1,
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
                  label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
-                 accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32, weight_std: bool = False, **opt):
+                 accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32, weight_std: bool = False,
+                 auto_augment: str = "none", **opt):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
@@ -136,6 +137,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         group = norm == "group"
         A.check(augment, augment_pad, spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
+        A.check_ta(auto_augment, spec.in_hw)
         _native.lib()
         self.K, self.O, self.E = K, O, E
         self._eval_cache = None  # evaluate_full's padded device copy of the last set passed
@@ -146,6 +148,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         # label smoothing, mixup and CutMix of the training loss / input, keyed the same way
         self.label_smoothing, self.mixup_alpha, self.cutmix_alpha = label_smoothing, mixup_alpha, cutmix_alpha
         self.mixes = mixup_alpha > 0 or cutmix_alpha > 0
+        self.auto_augment = auto_augment
         dev = self.device = torch.device(device)
         B = batch
         self.bn_momentum = bn_momentum
@@ -187,8 +190,18 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         # (record, oy, ox, flip) of every sample of the last training batch, written by input_aug /
         # input_mix; None with the pipeline off (input_norm feeds the network, as in every
         # evaluation path)
+        ta = auto_augment != "none"
         self.aug_out = (torch.zeros(B, 4, dtype=torch.int32, device=dev)
-                        if self.shuffle or augment != "none" or self.mixes else None)
+                        if self.shuffle or augment != "none" or self.mixes or ta else None)
+        # auto_augment (data/augment.py ta_apply): input_ta writes the u8 staging batch ta_x / ta_lab,
+        # which input_norm -- or input_mix, as a shard of B records -- turns into x0; ta_out is
+        # (op, bin, neg, 0) of every sample of the last training batch.  Off: none of this exists
+        self.ta_out = self.ta_x = self.ta_lab = self.ta_tab = None
+        if ta:
+            self.ta_out = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+            self.ta_x = torch.zeros(B, hw, hw, 3, dtype=torch.uint8, device=dev)
+            self.ta_lab = torch.zeros(B, dtype=torch.uint8, device=dev)
+            self.ta_tab = torch.from_numpy(A.ta_table().copy()).to(dev)
         # (partner, num, den, mode, x0, y0, x1, y1) of every sample of the last training batch, written
         # by input_mix and read by the soft-target loss; None with no mix.  mix_tab: the lambda
         # quantiles of each mode, built once (data/augment.py mix_tables)
@@ -328,7 +341,17 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
     def _forward_input(self, train: bool) -> None:
         """The batch at the cursor -> x0 / labels (the training input pipeline, or input_norm)."""
         K = self.K
-        if train and self.mixes:
+        if train and self.ta_out is not None:
+            K.input_ta(self.x, self.y, self.cursor, self.batch, self.ta_x, self.ta_lab, self.aug_out, self.ta_out,
+                       self.ta_tab, seed=self.seed, shuffle=self.shuffle, augment=self.augment, pad=self.augment_pad)
+            if self.mixes:  # over the staging batch: record j of B, no shuffle, crop or padding left to do
+                K.input_mix(self.ta_x, self.ta_lab, self.cursor, self.batch, self.x0, self.labels, None,
+                            self.mix_out, self.mix_tab, CIFAR_MEAN, CIFAR_STD, seed=self.seed, pad=0,
+                            mixup=self.mixup_alpha > 0, cutmix=self.cutmix_alpha > 0)
+            else:
+                K.input_norm(self.ta_x, self.ta_lab, self.cursor, self.batch, self.x0, self.labels, CIFAR_MEAN,
+                             CIFAR_STD)
+        elif train and self.mixes:
             K.input_mix(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, self.aug_out, self.mix_out,
                         self.mix_tab, CIFAR_MEAN, CIFAR_STD, seed=self.seed, shuffle=self.shuffle,
                         augment=self.augment, pad=self.augment_pad, mixup=self.mixup_alpha > 0,

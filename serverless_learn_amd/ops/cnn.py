@@ -329,7 +329,9 @@ def input_mix(x_u8, labels, cursor, batch: int, y, lab_out, params_out, mix_out,
         raise ValueError(f"input_mix: a sample's partner is another sample of its batch (batch >= 2), got {batch}")
     assert n >= batch and y.shape[0] == batch and tuple(y.shape[1:3]) == (h, w)
     assert labels.dtype == torch.uint8 and labels.numel() >= n and lab_out.numel() >= batch
-    assert params_out.dtype == torch.int32 and params_out.numel() == 4 * batch and params_out.is_contiguous()
+    # (None: not written -- the engine after input_ta, whose staging batch is the "shard" here)
+    assert params_out is None or (params_out.dtype == torch.int32 and params_out.numel() == 4 * batch
+                                  and params_out.is_contiguous())
     assert mix_out.dtype == torch.int32 and mix_out.numel() == 8 * batch and mix_out.is_contiguous()
     assert table.dtype == torch.int32 and tuple(table.shape) == (2, A.MIX_L) and table.is_contiguous()
     assert table.device == x_u8.device and cursor.dtype == torch.int32
@@ -337,6 +339,35 @@ def input_mix(x_u8, labels, cursor, batch: int, y, lab_out, params_out, mix_out,
     N.call("sl_input_mix", p(x_u8), p(labels), p(cursor), n, batch, h, w, pad, A.flags(shuffle, augment),
            seed & ((1 << 64) - 1), p(table), modes, _bf16(y), p(lab_out), p(params_out), p(mix_out),
            *[float(v) for v in mean], *[float(v) for v in std], N.stream_ptr())
+
+
+def input_ta(x_u8, labels, cursor, batch: int, ta_x, ta_lab, params_out, ta_out, table, seed: int = 0,
+             shuffle: bool = False, augment: str = "none", pad: int = 4, force: int = -1):
+    """TrivialAugment Wide (data/augment.py ``ta_apply``): sample j of the batch at ``cursor``, drawn,
+    cropped and mirrored as :func:`input_aug` does, gets one of the 14 operations at a random strength
+    -> the u8 staging batch ``ta_x`` [batch,H,W,3] and its labels ``ta_lab``, which :func:`input_norm`
+    or :func:`input_mix` turn into the network's input.  ``table`` is ``ta_table()`` on the device
+    (int32 [14, 31, 2, 8]); ``params_out`` is :func:`input_aug`'s; ``ta_out`` (int32 [batch, 4]) receives
+    each sample's (op, bin, neg, 0).  ``force = op | bin << 8 | neg << 16`` pins the draw of every
+    sample (tests); -1 draws.  One workgroup keeps one image in LDS: at most 4096 pixels."""
+    from ..data import augment as A
+
+    assert x_u8.dtype == torch.uint8 and x_u8.shape[-1] == 3 and x_u8.is_contiguous()
+    n, h, w = x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]
+    A.check(augment, pad, min(h, w))
+    if h * w > A.TA_MAX_PIXELS:
+        raise ValueError(f"input_ta: an image of {h} x {w} pixels does not fit the workgroup's LDS "
+                         f"(at most {A.TA_MAX_PIXELS} pixels)")
+    assert n >= batch >= 1 and labels.dtype == torch.uint8 and labels.numel() >= n
+    assert ta_x.dtype == torch.uint8 and tuple(ta_x.shape) == (batch, h, w, 3) and ta_x.is_contiguous()
+    assert ta_lab.dtype == torch.uint8 and ta_lab.numel() >= batch
+    for out in (params_out, ta_out):
+        assert out.dtype == torch.int32 and out.numel() == 4 * batch and out.is_contiguous()
+    assert table.dtype == torch.int32 and tuple(table.shape) == (len(A.TA_OPS), A.TA_BINS, 2, 8)
+    assert table.is_contiguous() and table.device == x_u8.device and cursor.dtype == torch.int32
+    N.call("sl_input_ta", p(x_u8), p(labels), p(cursor), n, batch, h, w, pad, A.flags(shuffle, augment),
+           seed & ((1 << 64) - 1), p(table), p(ta_x), p(ta_lab), p(params_out), p(ta_out), int(force),
+           N.stream_ptr())
 
 
 def cursor_bump(cursor):

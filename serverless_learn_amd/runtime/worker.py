@@ -163,6 +163,8 @@ class Worker:
         if (c.augment, c.augment_pad, c.shuffle) != ("none", 4, False):
             # (an unknown name or a bad pad is refused by the trainer, data/augment.py check)
             kw.update(augment=c.augment, augment_pad=c.augment_pad, shuffle=c.shuffle)
+        if c.auto_augment != "none":  # (Config refuses it for the MLP, the trainer an image that is too large)
+            kw.update(auto_augment=c.auto_augment)
         if (c.label_smoothing, c.mixup_alpha, c.cutmix_alpha) != (0, 0, 0):
             # (a mix with batch < 2 is refused by the trainer, data/augment.py check_mix)
             kw.update(label_smoothing=c.label_smoothing, mixup_alpha=c.mixup_alpha, cutmix_alpha=c.cutmix_alpha)
@@ -184,6 +186,10 @@ class Worker:
         self.trainer = make_trainer(self.cfg.model, self.device, **kw)
         if c.norm != "batch":
             self.log.info("norm", kind=c.norm, groups=int(c.norm_groups))
+        if c.auto_augment != "none":
+            from ..data.augment import TA_BINS, TA_OPS
+
+            self.log.info("auto_augment", policy=c.auto_augment, ops=len(TA_OPS), bins=TA_BINS)
         if c.weight_std:
             from ..models.resnet import WS_EPS
 
