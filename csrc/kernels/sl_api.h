@@ -22,6 +22,11 @@ struct BnBwdEpi;  // bn_bwd_epi.h
 
 extern "C" {
 
+// agc.hip: adaptive gradient clipping of the ResNet trainers, one wave per unit (agc_clip > 0)
+int sl_agc_clip(const float* w, float* grad, long total, const int* units_h, const int* units, int n_units,
+                const int* work_h, const int* work, int n_work, double clip, double eps, float* stats,
+                hipStream_t stream);
+
 // cnn_aux.hip
 long sl_rsum_floats(int n);
 long sl_rsum_result_offset(int n);

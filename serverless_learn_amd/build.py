@@ -44,8 +44,8 @@ KERNELS_DET_SO = os.path.join(NATIVE_DIR, "libslkernels_det.so")
 # per-file compiler flags on top of the common ones.  groupnorm.hip: scalar fp32 arithmetic only
 # (no packed v_pk_* forms), so its fixed-order sums round the same way in every instantiation
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-FILE_FLAGS = {"groupnorm.hip": _NO_PACKED_FP32, "lars.hip": _NO_PACKED_FP32, "muon.hip": _NO_PACKED_FP32,
-              "weight_std.hip": _NO_PACKED_FP32}
+FILE_FLAGS = {"agc.hip": _NO_PACKED_FP32, "groupnorm.hip": _NO_PACKED_FP32, "lars.hip": _NO_PACKED_FP32,
+              "muon.hip": _NO_PACKED_FP32, "weight_std.hip": _NO_PACKED_FP32}
 
 
 def _core_so_name() -> str:

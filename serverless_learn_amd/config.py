@@ -85,6 +85,9 @@ class Config:
     lr_decay_steps: int = 0            # step at which the decay ends (0 = max_steps)
     lr_min_ratio: float = 0.0          # the decay ends at lr_min_ratio * lr
     clip_grad_norm: float = 0.0        # clip the aggregated gradient to this global L2 norm (0 = off, inf = measure)
+    agc_clip: float = 0.0              # resnet18: adaptive gradient clipping, every filter's gradient held to agc_clip *
+                                       # max(its weights' norm, agc_eps), ahead of clip_grad_norm (0 = off)
+    agc_eps: float = 1e-3              # agc_clip: the floor under a unit's weight norm (> 0)
     accum_steps: int = 1               # micro-batches per optimizer step (one exchange, one clip, one update)
     global_batch: int = 0              # > 0: accum_steps is chosen at every membership change so that
                                        # accum_steps * batch * world is as close to this as it can be (0 = off)
@@ -152,6 +155,13 @@ class Config:
             check_muon(self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps)
             if self.optimizer == "muon" and self.model in ("mlp", "simulate"):
                 raise ValueError(f"optimizer='muon': the {self.model} model has no conv weight to orthogonalise "
+                                 "(model='resnet18')")
+        if (self.agc_clip, self.agc_eps) != (0.0, 1e-3):  # NaN included
+            from .ops.optim import check_agc
+
+            check_agc(self.agc_clip, self.agc_eps)
+            if self.agc_clip > 0 and self.model in ("mlp", "simulate"):
+                raise ValueError(f"agc_clip: the {self.model} model has no filter or norm vector to clip by "
                                  "(model='resnet18')")
         if isinstance(self.accum_steps, bool) or int(self.accum_steps) != self.accum_steps or self.accum_steps < 1:
             raise ValueError(f"accum_steps must be an integer >= 1, got {self.accum_steps!r}")

@@ -330,6 +330,19 @@ class ResNetModel:
         """Every BatchNorm layer's scale and shift (``spec_layout``'s names): decay class 1."""
         return tuple(b.name + sfx for b in self.spec.bns() for sfx in (".weight", ".bias"))
 
+    def _init_agc(self) -> None:
+        """agc_clip > 0: the units of adaptive gradient clipping (ops/optim.py agc_plan: every filter
+        row of every conv bank, every norm scale and shift; fc is left out) and, on a GPU, their
+        tables and the stats buffer.  Off, nothing is built or allocated."""
+        from ..ops import optim as O
+
+        if not self.opt.agcs:
+            return
+        if self._gpu:
+            O.require_kernels(self.opt, *O.AGC_KERNELS)
+        self.agc_plan = O.agc_plan(self.layout(), int(self.params.numel()), self.spec.convs(), self.norm_tensors())
+        self.agc_buf = O.AgcBuffers(self.agc_plan, self.device) if self._gpu else None
+
     def _model_extra(self) -> dict:
         d = {}
         for name, (rm, rv) in self.running_stats().items():
@@ -384,6 +397,7 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         self.last_mix = None
         self._init_cpu(flat if flat is not None else init_params(self.spec, seed), batch, lr, momentum,
                        weight_decay, world_size, accum_steps, opt)
+        self._init_agc()
         self.running = running_stats(self.spec) if norm == "batch" else {}
         self._norm_kw = dict(norm=norm, groups=self.norm_groups) if norm == "group" else {}
         self.weight_std = bool(weight_std)

@@ -161,6 +161,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.params = torch.zeros(n, dtype=torch.float32, device=dev)
         self.params.copy_((flat if flat is not None else init_params(spec, seed)).to(dev))
         self._init_state(batch, lr, momentum, weight_decay, world_size, accum_steps, opt)
+        self._init_agc()
         self.grad = torch.zeros_like(self.params)
         self.shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
         bns = [] if group else list(spec.bns())  # (GroupNorm: no statistics arena, no running statistics)
@@ -667,6 +668,8 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             self.allreduce(self.grad)
         self.phases.mark("exchange")
         self._unstandardize_grad()
+        if self.agc_buf is not None:  # unit by unit on the true dL/dw, ahead of the global clip (agc.hip)
+            self.O.agc_clip_flat(self.params, self.grad, self.agc_buf, self.opt.agc_clip, self.opt.agc_eps)
         if self.opt.clips:  # on the aggregated gradient, before the unchanged update rule
             self.O.clip_grad_norm_flat(self.grad, self.opt.clip_grad_norm, self.clip_partials, self.clip_norm)
         self._update()

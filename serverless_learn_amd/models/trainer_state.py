@@ -16,8 +16,9 @@ import numpy as np
 import torch
 
 from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, LARS_KERNELS, MUON_KERNELS, LarsBuffers,
-                         MuonBuffers, OptSpec, check_accum_steps, clip_buffers, clip_grad_, decay_vector, ema_update_,
-                         lars_plan, muon_plan, require_kernels, sgd_update, trainer_class_map)
+                         MuonBuffers, OptSpec, agc_clip_reference, agc_summary, check_accum_steps, clip_buffers,
+                         clip_grad_, decay_vector, ema_update_, lars_plan, muon_plan, require_kernels, sgd_update,
+                         trainer_class_map)
 
 
 @dataclass
@@ -59,6 +60,11 @@ class TrainerState:
     split-K partials); :meth:`muon_norms` reads the last update's ``||u||_F``.  The momentum, always
     allocated under Muon, is its only state.
 
+    With ``agc_clip > 0`` (ResNet trainers, under any rule) the owner sets ``agc_plan`` (ops/optim.py
+    agc_plan: the units, every conv filter row and every norm vector) and on a GPU ``agc_buf``, its
+    uploaded tables with the launch's stats rows; :meth:`agc_stats` reads the last step's.  Adaptive
+    clipping keeps no state at all; with it off both attributes are None.
+
     The owner sets ``params`` (``n_params`` real entries, then any padding) before
     :meth:`_init_state`, and keeps ``cursor`` (an int, or a 1-element tensor on the device)."""
 
@@ -67,6 +73,8 @@ class TrainerState:
     opt_kernels = ()              # entry points of the owner's step-counter rules
     group_kernels = ()            # ... and of those rules with decay groups on
     lars_capable = False          # optimizer="lars": the ResNet trainers (models/resnet.py ResNetModel)
+    agc_plan = agc_buf = None     # agc_clip > 0: the ResNet trainers' units (ResNetModel._init_agc)
+    _agc_rows = None              # CPU: the last step's (wn, gn, s) rows
     accum_kernels = ACCUM_KERNELS  # ... and of its accumulated step
     graph = None                  # a captured step (GPU engines: a slot of utils/graphs.py)
     grad = None                   # the aggregated gradient of the last step, as the optimizer took it
@@ -87,6 +95,9 @@ class TrainerState:
         if spec.muon and not self.lars_capable:
             raise ValueError("optimizer='muon' orthogonalises the momentum of a deep network's conv weights: the mlp "
                              "model's fused slab update has no per-tensor step (model='resnet18')")
+        if spec.agcs and not self.lars_capable:
+            raise ValueError("agc_clip holds every filter's gradient to its weights' norm: the mlp model's fused slab "
+                             "update cannot see a norm before it moves a weight (model='resnet18')")
         word =lambda: torch.zeros(1, dtype=torch.int32, device=self.device)  # noqa: E731
         self.mom = torch.zeros_like(self.params) if (momentum > 0 or spec.adamw or spec.muon) else None
         # AdamW's second moment (mom is its first); the optimizer step the update reads (and the
@@ -148,6 +159,8 @@ class TrainerState:
 
     # ---- the CPU reference update: the definition the GPU engines are tested against ----
     def _opt_update(self, g: torch.Tensor) -> None:
+        if self.agc_plan is not None:  # unit by unit, ahead of the global clip (timm's order)
+            self._agc_rows = agc_clip_reference(self.params, g, self.agc_plan, self.opt.agc_clip, self.opt.agc_eps)
         if self.opt.clips:
             self._grad_norm = clip_grad_(g, self.opt.clip_grad_norm)
         if self.opt_step is None:
@@ -194,6 +207,16 @@ class TrainerState:
         if self._gpu:
             return dict(zip(self.muon_plan.names, self.muon_buf.norms.tolist()))
         return dict(zip(self.muon_plan.names, self._muon_norms or ()))
+
+    def agc_stats(self) -> dict:
+        """``{tensor name: (units, clipped units, smallest s)}`` of the last step's adaptive gradient
+        clipping, for every conv weight (one unit per filter) and every norm scale and shift (one
+        unit each); on a GPU one read of the stats buffer.  Empty before the first step on the CPU."""
+        if not self.opt.agcs:
+            raise ValueError("this trainer does not clip adaptively (agc_clip=0): there are no agc statistics")
+        if self._gpu:
+            return agc_summary(self.agc_plan, self.agc_buf.stats.cpu().numpy())
+        return agc_summary(self.agc_plan, self._agc_rows.numpy()) if self._agc_rows is not None else {}
 
     def ema_flat(self) -> torch.Tensor:
         """A copy of the averaged parameters (``ema_decay > 0``)."""

@@ -33,6 +33,11 @@ are the reference, :func:`muon_plan` the host side (tensors, block map, tile tab
 :func:`muon_prep`, :func:`muon_gram`, :func:`muon_poly`, :func:`muon_apply` and
 :func:`sgd_flat_muon` the grouped launches (csrc/kernels/muon.hip).
 
+Adaptive gradient clipping (``agc_clip``, under any rule; ResNet trainers) runs ahead of the global
+clip: :func:`agc_clip_reference` is its float64 definition, :func:`agc_plan` its units (every conv
+filter row, every norm vector) and :func:`agc_clip_flat` the one grouped launch
+(csrc/kernels/agc.hip).
+
 A weight EMA (``ema_decay``) follows every update: :func:`ema_update_` is its reference,
 :func:`ema_table` the per-step coefficients and :func:`ema_flat` the one launch that applies them and
 advances its own device-resident counter.
@@ -408,6 +413,115 @@ def clip_grad_(g: torch.Tensor, max_norm: float) -> float:
     return total
 
 
+# ---- adaptive gradient clipping (Brock et al. 2021; timm's adaptive_clip_grad) ----
+AGC_FIELDS = 4         # ints per unit of the table (csrc/kernels/agc.hip AgcUnit)
+AGC_UNITS_PER_WG = 4   # units per workgroup, one per wave (AGC_WAVES)
+AGC_EXCLUDE = ("fc.weight", "fc.bias")  # the final linear layer is not clipped (the paper leaves it out)
+
+
+def check_agc(clip, eps) -> None:
+    """``agc_clip``: a finite float >= 0 (0: off); ``agc_eps``: a finite float > 0."""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)  # noqa: E731
+    if not num(clip) or clip < 0:
+        raise ValueError(f"agc_clip must be a finite number >= 0 (0: off), got {clip!r}")
+    if not num(eps) or eps <= 0:
+        raise ValueError(f"agc_eps must be a finite number > 0, got {eps!r}")
+
+
+@dataclass(frozen=True)
+class AgcPlan:
+    """:func:`agc_plan`'s result.  ``names``: the tensors that have units, in offset order; ``units``:
+    int32 ``[U][4]`` = (offset, n, cin, cin_real), the longest first (a 1-D unit has ``cin = cin_real
+    = n``); ``owner``: per unit, its tensor's index in ``names``; ``work``: int32 ``[W][2]`` = (first
+    unit, unit count), one workgroup of the launch each; ``n``: the vector's length.  Everything that
+    is reported per unit (the stats rows) is in ``units``' order."""
+    names: tuple
+    units: np.ndarray
+    owner: np.ndarray
+    work: np.ndarray
+    n: int
+
+
+def agc_plan(layout, n: int, convs, norm=()) -> AgcPlan:
+    """The units of adaptive gradient clipping in a flat vector of ``n`` elements.  ``convs``: the conv
+    banks (``ConvSpec``s: name, off, cout, k, cin, cin_real), every row ``W[co][k k cin]`` of which is
+    one unit; ``norm``: the names, in ``layout`` (``[name, shape, offset]`` per tensor), of the
+    normalisation layers' scales and shifts, each one unit as a whole.  Nothing else is clipped
+    (:data:`AGC_EXCLUDE`).  The units are sorted longest first (stable: offset order within a
+    length), so the launch's last workgroups hold the short ones.  Shapes are not judged here: the
+    launcher refuses what the kernel does not serve."""
+    n = int(n)
+    assert 0 < n < 2 ** 31, "the unit table holds int32 offsets"
+    at = {name: (shape, off) for name, shape, off in layout}
+    tensors = [(c.off, c.name + ".weight", c.cout, c.k * c.k * c.cin, c.cin, c.cin_real) for c in convs]
+    for name in norm:
+        shape, off = at[name]
+        tensors.append((off, name, 1, math.prod(shape), math.prod(shape), math.prod(shape)))
+    tensors.sort()
+    assert not {t[1] for t in tensors} & set(AGC_EXCLUDE), "the final linear layer is not clipped"
+    names, units, owner = [], [], []
+    for off, name, rows, k, cin, cin_real in tensors:
+        assert name in at and at[name][1] == off and math.prod(at[name][0]) == rows * k, f"{name} is not the layout's"
+        units += [(off + r * k, k, cin, cin_real) for r in range(rows)]
+        owner += [len(names)] * rows
+        names.append(name)
+    assert units, "nothing to clip"
+    order = sorted(range(len(units)), key=lambda i: -units[i][1])
+    work = [(u, min(AGC_UNITS_PER_WG, len(units) - u)) for u in range(0, len(units), AGC_UNITS_PER_WG)]
+    return AgcPlan(tuple(names), np.array([units[i] for i in order], dtype=np.int32).reshape(-1, AGC_FIELDS),
+                   np.array([owner[i] for i in order], dtype=np.int32), np.array(work, dtype=np.int32).reshape(-1, 2), n)
+
+
+def _agc_norms(x: torch.Tensor) -> torch.Tensor:
+    """The L2 norm of every row of the float64 matrix ``x``, safe at both ends of the fp32 range:
+    ``amax sqrt(sum (x / amax)^2)`` with ``amax = max |x|`` of the row.  A row of zeros has norm 0
+    (no division); a row holding an Inf or a NaN has a NaN norm (``x * 0`` stands in for the
+    quotient there), never ``+Inf``."""
+    amax = x.abs().amax(dim=1)  # (a NaN propagates)
+    ok = (amax > 0) & (amax < math.inf)
+    q = torch.where(ok[:, None], x / torch.where(ok, amax, 1.0)[:, None], x * 0.0)
+    return amax * (q * q).sum(dim=1).sqrt()
+
+
+def agc_clip_reference(flat, grad, plan: AgcPlan, clip: float, eps: float = 1e-3) -> torch.Tensor:
+    """Adaptive gradient clipping's definition, in place on the fp32 gradient ``grad``.  For every
+    unit of ``plan``, over its real columns (``col % cin < cin_real``) and in float64: ``wn = ||w||``
+    of ``flat``, ``gn = ||g||`` (:func:`_agc_norms`), ``t = clip max(wn, eps)`` (a NaN ``wn`` stays a
+    NaN).  A unit is clipped iff ``gn > t`` -- so not at ``gn = 0`` and not with a NaN norm -- and
+    then every stored element of it, padding columns included, becomes ``g * s`` in fp32 with ``s =
+    float32(t / gn)``; a unit that is not clipped is not written.  Returns the float64 ``[U][3]``
+    rows ``(wn, gn, s)`` in the plan's order, ``s = 1`` where nothing was clipped."""
+    assert grad.dtype == torch.float32 and flat.numel() >= plan.n and grad.numel() >= plan.n
+    units = torch.from_numpy(plan.units.astype(np.int64))
+    rows = torch.ones(len(units), 3, dtype=torch.float64)
+    for key in sorted({tuple(u[1:]) for u in plan.units.tolist()}):  # one gather per shape of unit
+        k, cin, cin_real = key
+        sel = ((units[:, 1:] == torch.tensor(key)).all(dim=1)).nonzero().reshape(-1)
+        idx = (units[sel, 0][:, None] + torch.arange(k)[None, :]).to(grad.device)
+        real = (torch.arange(k) % cin < cin_real).to(grad.device)
+        g = grad[idx]
+        wn, gn = _agc_norms(flat[idx][:, real].double()).cpu(), _agc_norms(g[:, real].double()).cpu()
+        t = float(clip) * torch.where(wn < float(eps), float(eps), wn)
+        clipped = gn > t
+        s = torch.where(clipped, t / gn, 1.0).float()
+        if bool(clipped.any()):
+            c = clipped.to(grad.device)
+            grad[idx[c]] = g[c] * s.to(grad.device)[c][:, None]
+        rows[sel] = torch.stack([wn, gn, s.double()], dim=1)
+    return rows
+
+
+def agc_summary(plan: AgcPlan, rows) -> dict:
+    """``{tensor name: (units, clipped units, smallest s)}`` from the ``(wn, gn, s)`` rows of one
+    step (``s < 1`` marks a clipped unit)."""
+    s = np.asarray(rows, dtype=np.float64).reshape(-1, 3)[:, 2]
+    out = {}
+    for t, name in enumerate(plan.names):
+        mine = s[plan.owner == t]
+        out[name] = (int(mine.size), int((mine < 1.0).sum()), float(mine.min()))
+    return out
+
+
 EMA_WARMUP_OFFSET = 10   # warm-up: decay_t = min(decay, (1 + t) / (10 + t))
 EMA_TABLE_MAX = 1 << 20  # entries of the warm-up table
 
@@ -494,6 +608,10 @@ class OptSpec:
     muon_lr_ratio: float = 1.0
     muon_nesterov: bool = True
     muon_ns_steps: int = 5
+    # adaptive gradient clipping ahead of clip_grad_norm and the update, under any rule (ResNet trainers): every
+    # conv filter and norm vector of the gradient is held to agc_clip * max(its weights' norm, agc_eps) (0: off)
+    agc_clip: float = 0.0
+    agc_eps: float = 1e-3
 
     def __post_init__(self):
         check_group_decay("norm_weight_decay", self.norm_weight_decay)
@@ -502,6 +620,7 @@ class OptSpec:
             raise ValueError(f"unknown optimizer {self.optimizer!r} (choose from {OPTIMIZERS})")
         check_lars(self.lars_eta, self.lars_eps)
         check_muon(self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps)
+        check_agc(self.agc_clip, self.agc_eps)
         if self.lr_schedule not in SCHEDULES:
             raise ValueError(f"unknown lr_schedule {self.lr_schedule!r} (choose from {SCHEDULES})")
         if self.lr_warmup_steps < 0 or self.lr_decay_steps < 0:
@@ -518,6 +637,10 @@ class OptSpec:
     @property
     def clips(self) -> bool:
         return self.clip_grad_norm > 0.0
+
+    @property
+    def agcs(self) -> bool:
+        return self.agc_clip > 0.0
 
     @property
     def emas(self) -> bool:
@@ -636,6 +759,8 @@ class OptSpec:
         if self.muon:
             d.update(muon_lr_ratio=self.muon_lr_ratio, muon_nesterov=bool(self.muon_nesterov),
                      muon_ns_steps=int(self.muon_ns_steps))
+        if self.agcs:
+            d.update(agc_clip=self.agc_clip, agc_eps=self.agc_eps)
         return d
 
 
@@ -879,6 +1004,35 @@ def sgd_flat_muon(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor, step: tor
     N.call("sl_sgd_flat_muon", N.ptr(w), N.ptr(g), N.ptr(mom), N.ptr(shadow), w.numel(), N.ptr(step), N.ptr(lr_tab),
            lr_tab.numel() if lr_tab is not None else 0, float(lr), float(momentum), wd, wd_norm, wd_bias, 1.0,
            float(lr_ratio), N.ptr(b.cls), N.ptr(b.block_map), *b._tab(), N.ptr(b.x[0]), N.ptr(b.x[1]), int(ns_steps),
+           N.stream_ptr())
+
+
+AGC_KERNELS = ("sl_agc_clip",)
+
+
+class AgcBuffers:
+    """An :class:`AgcPlan` on a device, uploaded once (the launcher checks the tables' host copies),
+    and what the launch writes: ``stats``, fp32 ``[U][3]`` = (wn, gn, s) of the last call in the
+    plan's order, ``s = 1`` for a unit it left alone."""
+
+    def __init__(self, plan: AgcPlan, device):
+        self.plan = plan
+        self.units_h, self.work_h = np.ascontiguousarray(plan.units), np.ascontiguousarray(plan.work)
+        self.units, self.work = torch.from_numpy(self.units_h).to(device), torch.from_numpy(self.work_h).to(device)
+        self.stats = torch.zeros(len(plan.units), 3, dtype=torch.float32, device=device)
+
+
+def agc_clip_flat(w: torch.Tensor, g: torch.Tensor, b: AgcBuffers, clip: float, eps: float = 1e-3) -> None:
+    """:func:`agc_clip_reference` on the device, in place on ``g``, in one grouped launch
+    (csrc/kernels/agc.hip): one wave per unit, the gradient row in registers from its load to its
+    store, both norms in fp64 by the same two passes, a unit that is not clipped not written.
+    ``b.stats`` receives every unit's ``(wn, gn, s)``.  No host synchronisation and no state between
+    calls, so a captured graph replays it; bit-identical from call to call and in both builds."""
+    assert w.is_cuda and w.dtype == torch.float32 and g.dtype == torch.float32
+    assert w.is_contiguous() and g.is_contiguous() and g.numel() == w.numel()
+    assert w.numel() >= b.plan.n and b.units.device == w.device
+    N.call("sl_agc_clip", N.ptr(w), N.ptr(g), w.numel(), b.units_h.ctypes.data, N.ptr(b.units), len(b.units_h),
+           b.work_h.ctypes.data, N.ptr(b.work), len(b.work_h), float(clip), float(eps), N.ptr(b.stats),
            N.stream_ptr())
 
 

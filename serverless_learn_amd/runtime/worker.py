@@ -160,6 +160,8 @@ class Worker:
                       lr_decay_steps=c.lr_decay_steps or c.max_steps, lr_min_ratio=c.lr_min_ratio)
         if c.clip_grad_norm != 0:  # under any rule (a negative value or NaN is refused by OptSpec)
             kw.update(clip_grad_norm=c.clip_grad_norm)
+        if c.agc_clip > 0:  # (Config refuses it for the MLP; a bad value is refused by Config and by OptSpec)
+            kw.update(agc_clip=c.agc_clip, agc_eps=c.agc_eps)
         if (c.augment, c.augment_pad, c.shuffle) != ("none", 4, False):
             # (an unknown name or a bad pad is refused by the trainer, data/augment.py check)
             kw.update(augment=c.augment, augment_pad=c.augment_pad, shuffle=c.shuffle)
@@ -207,6 +209,8 @@ class Worker:
         if c.optimizer == "muon":
             self.log.info("muon", lr_ratio=c.muon_lr_ratio, nesterov=bool(c.muon_nesterov), ns_steps=c.muon_ns_steps,
                           tensors=len(self.trainer.muon_plan.names))
+        if c.agc_clip > 0:
+            self.log.info("agc", clip=c.agc_clip, eps=c.agc_eps, units=len(self.trainer.agc_plan.units))
         if c.ema_decay != 0:
             self.log.info("ema",decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
         if self.cfg.sync in ("gossip", "ps"):
