@@ -1,6 +1,6 @@
 // The per-sample draw of the training input pipeline, shared by cnn_aux.hip (input_aug_kernel,
-// input_mix_kernel) and input_ta.hip (input_ta_kernel): one copy, so the three kernels agree on the
-// record, the offsets and the flip of a sample bit for bit.
+// input_mix_kernel), input_ta.hip (input_ta_kernel) and input_rrc.hip (input_rrc_kernel, the record
+// alone): one copy, so the kernels agree on the record, the offsets and the flip of a sample bit for bit.
 #pragma once
 #include <stdint.h>
 

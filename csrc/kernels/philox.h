@@ -1,7 +1,7 @@
 // Counter-based Philox4x32-10, shared by the shard generator (datagen.hip) and the input
-// pipeline (cnn_aux.hip input_aug_kernel, input_mix_kernel; input_ta.hip).  The fourth counter word
+// pipeline (cnn_aux.hip input_aug_kernel, input_mix_kernel; input_ta.hip; input_rrc.hip).  The fourth counter word
 // names the stream, so two users never collide under one seed: 0 = shard generation, 1 = epoch
-// shuffle, 2 = crop / flip, 3 = mixup / CutMix, 4 = TrivialAugment.
+// shuffle, 2 = crop / flip, 3 = mixup / CutMix, 4 = TrivialAugment, 5 = RandomResizedCrop.
 // numpy twin: serverless_learn_amd/data/device_synth.py philox4x32_10.
 #pragma once
 #include <stdint.h>

@@ -193,6 +193,11 @@ int sl_gn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const fl
               int N, int HW, int C, int G, float eps, hipStream_t stream);
 int sl_gn_param_fold(const float* ws, int N, int C, float* grad_gamma, float* grad_beta, hipStream_t stream);
 
+// input_rrc.hip: RandomResizedCrop + flip of the ResNet trainers' input pipeline (augment="rrc-flip")
+int sl_input_rrc(const uint8_t* x, const uint8_t* lab, const int* cursor, int n_records, int batch, int H, int W,
+                 int flags, unsigned long long seed, const int* table, uint8_t* rrc_x, uint8_t* rrc_lab,
+                 int* params_out, int* rrc_out, hipStream_t stream);
+
 // lars.hip: layer-wise trust ratios over the ResNet trainers' flat vector (optimizer="lars")
 int sl_lars_chunk();
 int sl_lars_norms(const float* w, const float* g, const int* chunks, int n_chunks, double* partials,

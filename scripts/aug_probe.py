@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """What the ResNet engine's input pipeline costs (profiles/r13_input), and what label smoothing,
-mixup and CutMix add to it (profiles/r14_mix).
+mixup and CutMix add to it (profiles/r14_mix), and what RandomResizedCrop costs (profiles/r27_rrc).
 
-Four measurements, each a process of its own so that each runs under its own time limit:
+Six measurements, each a process of its own so that each runs under its own time limit:
 
     timeout -k 10 300 python scripts/aug_probe.py kernel --out profiles/r13_input && \\
     timeout -k 10 600 python scripts/aug_probe.py step --out profiles/r13_input
     timeout -k 10 300 python scripts/aug_probe.py mix --out profiles/r14_mix && \\
     timeout -k 10 900 python scripts/aug_probe.py mix_step --out profiles/r14_mix
+    timeout -k 10 300 python scripts/aug_probe.py rrc --out profiles/r27_rrc && \\
+    timeout -k 10 600 python scripts/aug_probe.py rrc_step --out profiles/r27_rrc
 
 kernel  input_norm_kernel and input_aug_kernel with each combination of parts on (aug_off: neither,
         which no trainer launches -- the cost of the per-image layout alone), B = 1024 images
@@ -24,6 +26,12 @@ mix     input_mix_kernel (mixup, CutMix, either; shuffle + crop-flip on) against
         unchanged code in the same library, so they are the baseline.
 mix_step  the graph-replayed step with each of label_smoothing, mixup_alpha, cutmix_alpha on, and all
         three on top of shuffle + crop-flip, against all off: alternating, three runs each.
+
+rrc     input_rrc_kernel alone and followed by input_norm over its staging batch (what the engine
+        launches with augment="rrc-flip") against input_aug with both parts on and input_norm: the same
+        interleaved rounds, B = 1024 images of 32x32.
+rrc_step  the graph-replayed step with shuffle + rrc-flip against shuffle + crop-flip (unchanged code:
+        the step as it was) and against all off: alternating, three runs each.
 
 Each prints one JSON line and writes it to <out>/aug_probe_<what>.json.
 """
@@ -202,15 +210,85 @@ def mix_step(args) -> dict:
     return res
 
 
+def rrc(args) -> dict:
+    from serverless_learn_amd.data import augment as A
+    from serverless_learn_amd.models.resnet import CIFAR_MEAN, CIFAR_STD
+    from serverless_learn_amd.ops import cnn as K
+
+    dev = torch.device("cuda:0")
+    x, y = _shard(dev)
+    out = torch.empty(B, HW, HW, 8, dtype=torch.bfloat16, device=dev)
+    lab = torch.empty(B, dtype=torch.uint8, device=dev)
+    params = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    rrc_out = torch.empty(B, 8, dtype=torch.int32, device=dev)
+    rrc_x = torch.empty(B, HW, HW, 3, dtype=torch.uint8, device=dev)
+    rrc_lab = torch.empty(B, dtype=torch.uint8, device=dev)
+    table = torch.from_numpy(A.rrc_table(HW, 0.08).copy()).to(dev)
+    cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def rrc_only():
+        K.input_rrc(x, y, cursor, B, rrc_x, rrc_lab, params, rrc_out, table, seed=0, shuffle=True)
+
+    def rrc_norm():
+        rrc_only()
+        K.input_norm(rrc_x, rrc_lab, cursor, B, out, lab, CIFAR_MEAN, CIFAR_STD)
+
+    fns = {"input_norm": lambda: K.input_norm(x, y, cursor, B, out, lab, CIFAR_MEAN, CIFAR_STD),
+           "aug_both": lambda: K.input_aug(x, y, cursor, B, out, lab, params, CIFAR_MEAN, CIFAR_STD, seed=0, pad=4,
+                                           shuffle=True, augment="crop-flip"),
+           "rrc": rrc_only, "rrc_then_norm": rrc_norm}
+    for fn in fns.values():
+        _timed(fn, 20)
+    us = {name: [] for name in fns}
+    for r in range(args.rounds):
+        cursor.fill_(5 * r + 1)
+        for name, fn in fns.items():
+            us[name].append(1e3 * _timed(fn, args.launches))
+    res = {"what": "rrc", "batch": B, "hw": HW, "records": N, "launches": args.launches, "rounds": args.rounds,
+           "device": torch.cuda.get_device_name(0)}
+    for name, v in us.items():
+        res[name] = {"us_median": round(statistics.median(v), 3), "us_min": round(min(v), 3),
+                     "us_max": round(max(v), 3), "us_rounds": [round(t, 3) for t in v]}
+    return res
+
+
+def rrc_step(args) -> dict:
+    from serverless_learn_amd.models.resnet_engine import FusedResNetTrainer
+
+    dev = torch.device("cuda:0")
+    x, y = _shard(dev)
+    cases = (("off", {}), ("crop_flip", dict(shuffle=True, augment="crop-flip")),
+             ("rrc_flip", dict(shuffle=True, augment="rrc-flip")))
+    trainers = {}
+    for name, kw in cases:
+        tr = FusedResNetTrainer(batch=B, device=dev, seed=0, **kw)
+        tr.load_shard(x, y)
+        tr.step()
+        tr.capture(warmup=1)
+        _timed(tr.step, 10)
+        trainers[name] = tr
+    ms = {name: [] for name in trainers}
+    for _ in range(3):
+        for name, tr in trainers.items():
+            ms[name].append(_timed(tr.step, args.steps))
+    res = {"what": "rrc_step", "batch": B, "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    for name, v in ms.items():
+        res[name] = {"ms_runs": [round(t, 4) for t in v], "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                     "ms_median": round(statistics.median(v), 4), "loss": round(trainers[name].stats().loss, 4)}
+    res["crop_flip_spread_ms"] = round(res["crop_flip"]["ms_max"] - res["crop_flip"]["ms_min"], 4)
+    res["rrc_minus_crop_flip_ms"] = round(res["rrc_flip"]["ms_median"] - res["crop_flip"]["ms_median"], 4)
+    return res
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("what", choices=["kernel", "step", "mix", "mix_step"])
+    ap.add_argument("what", choices=["kernel", "step", "mix", "mix_step", "rrc", "rrc_step"])
     ap.add_argument("--out", default="")
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=60)
     args = ap.parse_args(argv)
-    res = {"kernel": kernel, "step": step, "mix": mix, "mix_step": mix_step}[args.what](args)
+    res = {"kernel": kernel, "step": step, "mix": mix, "mix_step": mix_step, "rrc": rrc, "rrc_step": rrc_step}[args.what](args)
     line = json.dumps(res)
     print(line)
     if args.out:

@@ -94,8 +94,10 @@ class Config:
     ema_decay: float = 0.0             # > 0: keep an exponential moving average of the weights, updated after every
                                        # optimizer step (0 = off; < 1)
     ema_warmup: bool = True            # decay_t = min(ema_decay, (1 + t) / (10 + t)): early updates weigh more
-    augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip, data/augment.py)
+    augment: str = "none"              # resnet18: none | crop-flip (random crop + horizontal flip) | rrc-flip
+                                       # (RandomResizedCrop + horizontal flip), data/augment.py
     augment_pad: int = 4               # crop-flip: black pixels of padding around the image the crop is taken from
+    rrc_min_scale: float = 0.08        # rrc-flip: the smallest crop, as a fraction of the image's area (0 < s <= 1)
     shuffle: bool = False              # resnet18: draw each epoch's records through a fresh permutation of the shard
     auto_augment: str = "none"         # resnet18: none | trivial-wide (TrivialAugment Wide: one random operation per
                                        # image after crop / flip, data/augment.py; images up to 64 x 64)
@@ -182,6 +184,10 @@ class Config:
         if (self.augment, self.augment_pad, self.shuffle) != ("none", 4, False) and self.model in ("mlp", "simulate"):
             # the MLP kernels read X from bricks tiled once per shard: a per-sample gather would undo that
             raise ValueError(f"augment / shuffle: the {self.model} model has no input pipeline (model='resnet18')")
+        if self.rrc_min_scale != 0.08:  # NaN included
+            from .data.augment import check_rrc
+
+            check_rrc(self.rrc_min_scale)  # (an image the kernel does not serve is refused by the trainer)
         if self.auto_augment != "none":
             from .data.augment import check_ta
 

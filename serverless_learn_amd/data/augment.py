@@ -41,8 +41,18 @@ the batch within it.  All arithmetic is on unsigned 32-bit integers.
   ``input_ta_kernel`` (csrc/kernels/input_ta.hip) read the same integers and do integer arithmetic
   only, so they agree bit for bit.  The operations are written out at :func:`ta_apply`.
 
+* **RandomResizedCrop + flip** (``augment="rrc-flip"``; in place of crop / flip, ``augment_pad``
+  unused).  For try ``k = 0..9``, ``R = philox4x32_10(t, k, j, 5; seed)`` indexes :func:`rrc_table` at
+  ``[R.x >> 24][R.y >> 24]``: 256 areas between ``rrc_min_scale`` and 1 of the image by 256 log-uniform
+  aspect ratios in 3/4..4/3, each a box ``w | h << 16`` or 0 where the box does not fit.  The first
+  entry that fits is the crop, at ``top = R.z % (O - h + 1)``, ``left = R.w % (O - w + 1)``; ten misses
+  take the whole image (torchvision's fallback for a square image).  ``flip`` is
+  ``philox4x32_10(t, 10, j, 5; seed).x & 1``.  The box is resized back to ``O x O`` bilinearly with
+  half-pixel centres, separably, in integers with one rounding (:func:`rrc_apply`); every float of the
+  method lives in the table.  ``input_rrc_kernel`` (csrc/kernels/input_rrc.hip) equals it bit for bit.
+
 The shard generator uses Philox's fourth counter word 0 (data/device_synth.py); the streams here
-use 1, 2, 3 and 4, so they never collide with it under one seed.
+use 1, 2, 3, 4 and 5, so they never collide with it under one seed.
 """
 from __future__ import annotations
 
@@ -53,9 +63,13 @@ import numpy as np
 
 from .device_synth import MASK, philox4x32_10
 
-AUGMENTS = ("none", "crop-flip")
+AUGMENTS = ("none", "crop-flip", "rrc-flip")
 STREAM_SHUFFLE, STREAM_CROP, STREAM_MIX = 1, 2, 3
 STREAM_TA = 4
+STREAM_RRC = 5
+RRC_L = 256  # areas, and aspect ratios, of an RRC table (an index is the top 8 bits of a Philox word)
+RRC_TRIES = 10
+RRC_MIN_HW, RRC_MAX_HW = 4, 256  # input_rrc_kernel: a side that is a multiple of 4 in this range
 AUTO_AUGMENTS = ("none", "trivial-wide")
 TA_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
           "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")  # torchvision's order
@@ -138,8 +152,8 @@ def batch_params(seed: int, t: int, n: int, batch: int, pad: int, shuffle: bool,
     out[:, 1:] = (pad, pad, 0)
     if augment == "crop-flip":
         out[:, 1], out[:, 2], out[:, 3] = draws(seed, t, batch, pad)
-    elif augment != "none":
-        raise ValueError(f"unknown augment {augment!r} (choose from {AUGMENTS})")
+    elif augment != "none":  # ("rrc-flip" has rows of its own: rrc_params)
+        raise ValueError(f"batch_params: augment {augment!r} (choose from ('none', 'crop-flip'))")
     return out
 
 
@@ -430,4 +444,85 @@ def ta_apply(a_u8: np.ndarray, ta: np.ndarray, table: np.ndarray | None = None) 
     out = np.empty(a.shape, np.uint8)
     for j, (op, b, neg, _) in enumerate(np.asarray(ta)):
         out[j] = _ta_one(a[j].astype(np.int64), int(op), tab[op, b, neg])
+    return out
+
+
+# ---- RandomResizedCrop + flip ----
+def check_rrc(min_scale: float, in_hw: int | None = None) -> None:
+    """Refuse what no trainer implements (Config and both trainers call this)."""
+    if not (math.isfinite(min_scale) and 0 < min_scale <= 1):
+        raise ValueError(f"rrc_min_scale must be finite and in (0, 1], got {min_scale!r}")
+    if in_hw is not None and not (RRC_MIN_HW <= in_hw <= RRC_MAX_HW and in_hw % 4 == 0):
+        raise ValueError(f"augment='rrc-flip': the image side must be a multiple of 4 in {RRC_MIN_HW}..{RRC_MAX_HW} "
+                         f"(the kernel's four-pixel stores and its LDS band), got {in_hw}")
+
+
+@functools.lru_cache(maxsize=None)
+def rrc_table(O: int, min_scale: float = 0.08) -> np.ndarray:
+    """int32 [256, 256] (area, ratio): entry ``(s, r)`` is the box of area ``O O (min_scale +
+    (1 - min_scale)(s + 0.5) / 256)`` and aspect ratio ``exp(log(3/4) + (log(4/3) - log(3/4))(r + 0.5) /
+    256)`` as ``w | h << 16``, sides rounded to the nearest integer in float64; 0 where a side is 0
+    or larger than ``O`` (torchvision redraws)."""
+    check_rrc(min_scale)
+    u = (np.arange(RRC_L, dtype=np.float64) + 0.5) / RRC_L
+    area = (float(O) * O * (min_scale + (1.0 - min_scale) * u))[:, None]
+    q = np.exp(math.log(3 / 4) + (math.log(4 / 3) - math.log(3 / 4)) * u)[None, :]
+    w, h = np.rint(np.sqrt(area * q)).astype(np.int64), np.rint(np.sqrt(area / q)).astype(np.int64)
+    ok = (w > 0) & (w <= O) & (h > 0) & (h <= O)
+    tab = np.where(ok, w | (h << 16), 0).astype(np.int32)
+    tab.setflags(write=False)
+    return tab
+
+
+def rrc_params(seed: int, t: int, n: int, batch: int, O: int, shuffle: bool, table: np.ndarray) -> np.ndarray:
+    """int32 [batch, 8] of (record, top, left, h, w, flip, tries, fallback) at cursor ``t``.  An entry
+    of ``table`` whose box does not fit ``O`` counts as 0, as the kernel reads it."""
+    out = np.zeros((batch, 8), np.int32)
+    out[:, 0] = batch_params(seed, t, n, batch, 0, shuffle, "none")[:, 0]
+    out[:, 3:5], out[:, 6:] = O, (RRC_TRIES, 1)  # ten misses: the whole image
+    keys, js = _keys(seed), np.arange(batch, dtype=np.uint64)
+    tab = np.asarray(table).astype(np.int64).reshape(RRC_L, RRC_L)
+    todo = np.ones(batch, bool)
+    for k in range(RRC_TRIES):
+        r = philox4x32_10(t, k, js, STREAM_RRC, *keys)
+        e = tab[(r[0] >> np.uint64(24)).astype(np.int64), (r[1] >> np.uint64(24)).astype(np.int64)]
+        w, h = e & 0xFFFF, (e >> 16) & 0xFFFF
+        hit = todo & (w > 0) & (w <= O) & (h > 0) & (h <= O)
+        top = r[2].astype(np.int64) % np.where(hit, O - h + 1, 1)
+        left = r[3].astype(np.int64) % np.where(hit, O - w + 1, 1)
+        out[hit] = np.stack([out[:, 0], top, left, h, w, out[:, 5], np.full(batch, k + 1), np.zeros(batch, np.int64)],
+                            1)[hit]
+        todo &= ~hit
+    out[:, 5] = philox4x32_10(t, RRC_TRIES, js, STREAM_RRC, *keys)[0] & np.uint64(1)
+    return out
+
+
+def rrc_taps(n: int, O: int):
+    """(i0, i1, f) of the ``O`` output positions along an axis whose crop is ``n`` long: the two source
+    taps within the crop and the second one's weight in 0..256.  The centre of output ``i`` lies at
+    ``((2i + 1) n - O) / 2O``; with ``num = (2i + 1) n + O`` (never negative), ``s = num // 2O - 1`` is its
+    floor and ``f = ((num - (s + 1) 2O) 256 + O) // 2O`` the fraction, rounded to Q8."""
+    num = (2 * np.arange(O, dtype=np.int64) + 1) * n + O
+    s = num // (2 * O) - 1
+    f = ((num - (s + 1) * 2 * O) * 256 + O) // (2 * O)
+    return np.clip(s, 0, n - 1), np.clip(s + 1, 0, n - 1), f
+
+
+def rrc_apply(x_u8: np.ndarray, params: np.ndarray) -> np.ndarray:
+    """The u8 [B, O, O, 3] batch of :func:`rrc_params` rows over the shard ``x_u8`` [N, O, O, 3]: each
+    box resized to ``O x O``, bilinear with half-pixel centres (``align_corners=False``).  Horizontally
+    ``hr = a (256 - fx) + b fx`` (16 bits, exact), then ``(hr0 (256 - fy) + hr1 fy + 32768) >> 16``: one
+    rounding.  With ``flip`` output column ``x`` takes the value of column ``O - 1 - x``."""
+    x_u8 = np.asarray(x_u8)
+    _, hh, O, ch = x_u8.shape
+    if hh != O:
+        raise ValueError(f"rrc_apply: square images, got {hh} x {O}")
+    out = np.empty((len(params), O, O, ch), np.uint8)
+    for j, (rec, top, left, h, w, flip, _, _) in enumerate(np.asarray(params)):
+        src = x_u8[rec, top:top + h, left:left + w].astype(np.int64)
+        x0, x1, fx = rrc_taps(int(w), O)
+        y0, y1, fy = rrc_taps(int(h), O)
+        hr = src[:, x0] * (256 - fx)[None, :, None] + src[:, x1] * fx[None, :, None]
+        v = (hr[y0] * (256 - fy)[:, None, None] + hr[y1] * fy[:, None, None] + 32768) >> 16
+        out[j] = v[:, ::-1] if flip else v
     return out

@@ -372,7 +372,7 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
                  flat: torch.Tensor | None = None, in_hw: int | None = None, augment: str = "none",
                  augment_pad: int = 4, shuffle: bool = False, label_smoothing: float = 0.0, mixup_alpha: float = 0.0,
                  cutmix_alpha: float = 0.0, accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32,
-                 weight_std: bool = False, auto_augment: str = "none", **opt):
+                 weight_std: bool = False, auto_augment: str = "none", rrc_min_scale: float = 0.08, **opt):
         from ..data import augment as A
 
         if isinstance(classes, bool) or int(classes) != classes or not 1 <= classes <= 256:
@@ -382,6 +382,11 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         A.check(augment, augment_pad, self.spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         A.check_ta(auto_augment, self.spec.in_hw)
+        A.check_rrc(rrc_min_scale, self.spec.in_hw if augment == "rrc-flip" else None)
+        # augment="rrc-flip" (data/augment.py rrc_apply) in place of crop / flip; last_rrc is the last
+        # batch's (record, top, left, h, w, flip, tries, fallback), None with it off
+        self.rrc_min_scale = rrc_min_scale
+        self.last_rrc = None
         # TrivialAugment Wide between crop / flip and the mix (data/augment.py ta_apply); ta_out is the
         # last batch's (op, bin, neg, 0), None with it off
         self.auto_augment = auto_augment
@@ -421,9 +426,16 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         mixes = self.mixup_alpha > 0 or self.cutmix_alpha > 0
         ta = self.auto_augment != "none"
         if self.shuffle or self.augment != "none" or mixes or ta:
-            self.last_aug = A.batch_params(self.seed, self.cursor, self.x.shape[0], self.batch, self.augment_pad,
-                                           self.shuffle, self.augment)
-            xs = A.apply(self.x.cpu().numpy(), self.last_aug, self.augment_pad)
+            if self.augment == "rrc-flip":
+                hw = self.spec.in_hw
+                self.last_rrc = A.rrc_params(self.seed, self.cursor, self.x.shape[0], self.batch, hw, self.shuffle,
+                                             A.rrc_table(hw, self.rrc_min_scale))
+                self.last_aug = np.ascontiguousarray(self.last_rrc[:, [0, 1, 2, 5]])  # (record, top, left, flip)
+                xs = A.rrc_apply(self.x.cpu().numpy(), self.last_rrc)
+            else:
+                self.last_aug = A.batch_params(self.seed, self.cursor, self.x.shape[0], self.batch, self.augment_pad,
+                                               self.shuffle, self.augment)
+                xs = A.apply(self.x.cpu().numpy(), self.last_aug, self.augment_pad)
             if ta:
                 self.ta_out = A.ta_params(self.seed, self.cursor, self.batch)
                 xs = A.ta_apply(xs, self.ta_out)

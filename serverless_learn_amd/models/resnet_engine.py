@@ -9,7 +9,8 @@ cursor, like the MLP engine).
 
 Per step:
   forward   input_norm (input_aug with shuffle= / augment= on, input_mix with mixup_alpha= /
-            cutmix_alpha= on, input_ta in front of either with auto_augment= on: data/augment.py) ->
+            cutmix_alpha= on, input_ta in front of either with auto_augment= on, input_rrc in front
+            of all of them with augment="rrc-flip": data/augment.py) ->
             [conv (+BN stats in the epilogue) -> bn_apply with
             the finalize folded in (+residual, ReLU)] x 20 -> avgpool -> fc ->
             softmax-CE (loss, dlogits, dbias; against soft targets with a mix or
@@ -119,7 +120,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                  in_hw: int | None = None, augment: str = "none", augment_pad: int = 4, shuffle: bool = False,
                  label_smoothing: float = 0.0, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
                  accum_steps: int = 1, norm: str = "batch", norm_groups: int = 32, weight_std: bool = False,
-                 auto_augment: str = "none", **opt):
+                 auto_augment: str = "none", rrc_min_scale: float = 0.08, **opt):
         from ..data import augment as A
         from ..ops import _native
         from ..ops import cnn as K
@@ -138,6 +139,8 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         A.check(augment, augment_pad, spec.in_hw)
         A.check_mix(label_smoothing, mixup_alpha, cutmix_alpha, batch)
         A.check_ta(auto_augment, spec.in_hw)
+        rrc = augment == "rrc-flip"
+        A.check_rrc(rrc_min_scale, spec.in_hw if rrc else None)
         _native.lib()
         self.K, self.O, self.E = K, O, E
         self._eval_cache = None  # evaluate_full's padded device copy of the last set passed
@@ -148,7 +151,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         # label smoothing, mixup and CutMix of the training loss / input, keyed the same way
         self.label_smoothing, self.mixup_alpha, self.cutmix_alpha = label_smoothing, mixup_alpha, cutmix_alpha
         self.mixes = mixup_alpha > 0 or cutmix_alpha > 0
-        self.auto_augment = auto_augment
+        self.auto_augment, self.rrc_min_scale = auto_augment, rrc_min_scale
         dev = self.device = torch.device(device)
         B = batch
         self.bn_momentum = bn_momentum
@@ -203,6 +206,19 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             self.ta_x = torch.zeros(B, hw, hw, 3, dtype=torch.uint8, device=dev)
             self.ta_lab = torch.zeros(B, dtype=torch.uint8, device=dev)
             self.ta_tab = torch.from_numpy(A.ta_table().copy()).to(dev)
+        # augment="rrc-flip" (data/augment.py rrc_apply): input_rrc goes first and writes the u8 staging
+        # batch rrc_x / rrc_lab, which input_ta, input_mix or input_norm read as a shard of B records;
+        # rrc_out is (record, top, left, h, w, flip, tries, fallback) of every sample of the last
+        # training batch, and aug_out its (record, top, left, flip) -- input_ta's own rows, over the
+        # staging batch, go to rrc_scratch.  Off: none of this exists
+        self.rrc_out = self.rrc_x = self.rrc_lab = self.rrc_tab = self.rrc_scratch = None
+        if rrc:
+            self.rrc_out = torch.zeros(B, 8, dtype=torch.int32, device=dev)
+            self.rrc_x = torch.zeros(B, hw, hw, 3, dtype=torch.uint8, device=dev)
+            self.rrc_lab = torch.zeros(B, dtype=torch.uint8, device=dev)
+            self.rrc_tab = torch.from_numpy(A.rrc_table(hw, rrc_min_scale).copy()).to(dev)
+            if ta:
+                self.rrc_scratch = torch.zeros(B, 4, dtype=torch.int32, device=dev)
         # (partner, num, den, mode, x0, y0, x1, y1) of every sample of the last training batch, written
         # by input_mix and read by the soft-target loss; None with no mix.  mix_tab: the lambda
         # quantiles of each mode, built once (data/augment.py mix_tables)
@@ -342,7 +358,9 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
     def _forward_input(self, train: bool) -> None:
         """The batch at the cursor -> x0 / labels (the training input pipeline, or input_norm)."""
         K = self.K
-        if train and self.ta_out is not None:
+        if train and self.rrc_out is not None:
+            self._forward_input_rrc()
+        elif train and self.ta_out is not None:
             K.input_ta(self.x, self.y, self.cursor, self.batch, self.ta_x, self.ta_lab, self.aug_out, self.ta_out,
                        self.ta_tab, seed=self.seed, shuffle=self.shuffle, augment=self.augment, pad=self.augment_pad)
             if self.mixes:  # over the staging batch: record j of B, no shuffle, crop or padding left to do
@@ -363,6 +381,23 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                         pad=self.augment_pad)
         else:
             K.input_norm(self.x, self.y, self.cursor, self.batch, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)
+
+    def _forward_input_rrc(self) -> None:
+        """augment="rrc-flip": input_rrc, then the unchanged kernels over its staging batch -- record j
+        of B at every cursor, with no shuffle, crop or padding left to do."""
+        K, B = self.K, self.batch
+        K.input_rrc(self.x, self.y, self.cursor, B, self.rrc_x, self.rrc_lab, self.aug_out, self.rrc_out,
+                    self.rrc_tab, seed=self.seed, shuffle=self.shuffle)
+        xs, ys = self.rrc_x, self.rrc_lab
+        if self.ta_out is not None:
+            K.input_ta(xs, ys, self.cursor, B, self.ta_x, self.ta_lab, self.rrc_scratch, self.ta_out, self.ta_tab,
+                       seed=self.seed, pad=0)
+            xs, ys = self.ta_x, self.ta_lab
+        if self.mixes:
+            K.input_mix(xs, ys, self.cursor, B, self.x0, self.labels, None, self.mix_out, self.mix_tab, CIFAR_MEAN,
+                        CIFAR_STD, seed=self.seed, pad=0, mixup=self.mixup_alpha > 0, cutmix=self.cutmix_alpha > 0)
+        else:
+            K.input_norm(xs, ys, self.cursor, B, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)
 
     def forward(self, train: bool = True):
         if self.norm == "group":

@@ -370,6 +370,33 @@ def input_ta(x_u8, labels, cursor, batch: int, ta_x, ta_lab, params_out, ta_out,
            N.stream_ptr())
 
 
+def input_rrc(x_u8, labels, cursor, batch: int, rrc_x, rrc_lab, params_out, rrc_out, table, seed: int = 0,
+              shuffle: bool = False):
+    """RandomResizedCrop + flip (data/augment.py ``rrc_params`` / ``rrc_apply``): sample j of the batch at
+    ``cursor`` -- drawn through the epoch's permutation with ``shuffle`` -- is a random box of its record
+    resized bilinearly back to the record's size and mirrored at random -> the u8 staging batch
+    ``rrc_x`` [batch,O,O,3] and its labels ``rrc_lab``, which :func:`input_ta`, :func:`input_mix` or
+    :func:`input_norm` turn into the network's input.  ``table`` is ``rrc_table(O, min_scale)`` on the
+    device (int32 [256, 256]; tests pass tables of their own); ``params_out`` (int32 [batch, 4]) receives
+    each sample's (record, top, left, flip), ``rrc_out`` (int32 [batch, 8]) its (record, top, left, h, w,
+    flip, tries, fallback).  One workgroup resamples a band of 16 output rows of one image."""
+    from ..data import augment as A
+
+    assert x_u8.dtype == torch.uint8 and x_u8.dim() == 4 and x_u8.shape[-1] == 3 and x_u8.is_contiguous()
+    n, h, w = x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]
+    assert labels.dtype == torch.uint8 and labels.numel() >= n
+    assert rrc_x.dtype == torch.uint8 and tuple(rrc_x.shape) == (batch, h, w, 3) and rrc_x.is_contiguous()
+    assert rrc_lab.dtype == torch.uint8 and rrc_lab.numel() >= batch
+    for out, cols in ((params_out, 4), (rrc_out, 8)):
+        assert out.dtype == torch.int32 and out.numel() == cols * batch and out.is_contiguous()
+    assert table.dtype == torch.int32 and tuple(table.shape) == (A.RRC_L, A.RRC_L)
+    assert table.is_contiguous() and table.device == x_u8.device and cursor.dtype == torch.int32
+    # (a shape the kernel does not serve -- not square, a side outside 4..256 or no multiple of 4, fewer
+    # records than one batch -- is refused by the launcher: N.call raises RuntimeError)
+    N.call("sl_input_rrc", p(x_u8), p(labels), p(cursor), n, batch, h, w, A.flags(shuffle, "none"),
+           seed & ((1 << 64) - 1), p(table), p(rrc_x), p(rrc_lab), p(params_out), p(rrc_out), N.stream_ptr())
+
+
 def cursor_bump(cursor):
     N.call("sl_cursor_bump", p(cursor), N.stream_ptr())
 

@@ -165,6 +165,8 @@ class Worker:
         if (c.augment, c.augment_pad, c.shuffle) != ("none", 4, False):
             # (an unknown name or a bad pad is refused by the trainer, data/augment.py check)
             kw.update(augment=c.augment, augment_pad=c.augment_pad, shuffle=c.shuffle)
+        if c.augment == "rrc-flip":
+            kw.update(rrc_min_scale=c.rrc_min_scale)
         if c.auto_augment != "none":  # (Config refuses it for the MLP, the trainer an image that is too large)
             kw.update(auto_augment=c.auto_augment)
         if (c.label_smoothing, c.mixup_alpha, c.cutmix_alpha) != (0, 0, 0):
@@ -192,6 +194,11 @@ class Worker:
             from ..data.augment import TA_BINS, TA_OPS
 
             self.log.info("auto_augment", policy=c.auto_augment, ops=len(TA_OPS), bins=TA_BINS)
+        if c.augment == "rrc-flip":
+            from ..data.augment import rrc_table
+
+            accepted = float((rrc_table(self.trainer.spec.in_hw, c.rrc_min_scale) != 0).mean())
+            self.log.info("rrc", min_scale=float(c.rrc_min_scale), accepted=round(accepted, 4))
         if c.weight_std:
             from ..models.resnet import WS_EPS
 
