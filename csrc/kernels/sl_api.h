@@ -287,6 +287,14 @@ int sl_mlp_opt_xgmi_groups(int rule, float* w, float* mom, float* v, float lr, f
                            int lr_n, float b1, float b2, float omb1, float omb2, float lnb1, float lnb2, float eps,
                            float wd_bias, hipStream_t stream);
 
+// sam.hip: sharpness-aware minimization's perturbation of the ResNet trainers' flat vector (sam_rho > 0)
+int sl_sam_chunk();
+int sl_sam_norms(const float* w, const float* g, const uint8_t* cls, long n, int adaptive, double eta,
+                 double* partials, int n_chunks, hipStream_t stream);
+int sl_sam_scale(const double* partials, int n_chunks, double rho, double* sam_buf, hipStream_t stream);
+int sl_sam_perturb(float* w, const float* g, float* saved, uint16_t* shadow, long n, const uint8_t* cls, int adaptive,
+                   double eta, const double* sam_buf, hipStream_t stream);
+
 // weight_std.hip: grouped wave-per-filter weight standardization of the ResNet trainers (weight_std=True)
 int sl_wstd_fwd(const float* w, uint16_t* shadow, float* stats_out, long total, const int* tensors_h,
                 const int* tensors, int T, const int* work_h, const int* work, int n_work, double eps,

@@ -88,6 +88,10 @@ class Config:
     agc_clip: float = 0.0              # resnet18: adaptive gradient clipping, every filter's gradient held to agc_clip *
                                        # max(its weights' norm, agc_eps), ahead of clip_grad_norm (0 = off)
     agc_eps: float = 1e-3              # agc_clip: the floor under a unit's weight norm (> 0)
+    sam_rho: float = 0.0               # resnet18: sharpness-aware minimization, the update's gradient taken at weights
+                                       # moved this far along the local gradient (0 = off; two passes per step)
+    sam_adaptive: bool = False         # sam_rho: ASAM, the conv / linear weights' move scaled by |w| + sam_eta
+    sam_eta: float = 0.01              # sam_adaptive: the floor under |w| (> 0)
     accum_steps: int = 1               # micro-batches per optimizer step (one exchange, one clip, one update)
     global_batch: int = 0              # > 0: accum_steps is chosen at every membership change so that
                                        # accum_steps * batch * world is as close to this as it can be (0 = off)
@@ -173,6 +177,15 @@ class Config:
             raise ValueError("accum_steps and global_batch: set one of them (global_batch chooses accum_steps)")
         if 0 < self.global_batch < self.batch:
             raise ValueError(f"global_batch {self.global_batch} is smaller than one worker's batch {self.batch}")
+        if (self.sam_rho, self.sam_adaptive, self.sam_eta) != (0.0, False, 0.01):  # NaN included
+            from .ops.optim import check_sam
+
+            check_sam(self.sam_rho, self.sam_adaptive, self.sam_eta)
+            if self.sam_rho > 0 and self.model in ("mlp", "simulate"):
+                raise ValueError(f"sam_rho: the {self.model} model has no second forward / backward in its step "
+                                 "(model='resnet18')")
+            if self.sam_rho > 0 and (self.accum_steps != 1 or self.global_batch > 0):
+                raise ValueError("sam_rho: a sharpness-aware step has no accumulated form (accum_steps=1, global_batch=0)")
         if (self.accum_steps != 1 or self.global_batch > 0) and self.model == "simulate":
             raise ValueError("accum_steps / global_batch: the simulate model has no gradient to accumulate")
         if self.ema_decay != 0:  # NaN included

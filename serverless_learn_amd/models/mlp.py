@@ -385,6 +385,8 @@ class FusedMLPTrainer(GraphedStep, TrainerState):
             raise ValueError("the weight EMA is switched on or off at construction (build a new trainer)")
         if new.agcs:
             raise ValueError("agc_clip: the mlp model's fused slab update cannot see a norm before it moves a weight")
+        if new.sams:
+            raise ValueError("sam_rho: the mlp model's fused step has no second forward / backward")
         if new.clips and self.xgmi is not None:
             raise ValueError("gradient clipping is not available with the xGMI exchange")
         self.opt = new

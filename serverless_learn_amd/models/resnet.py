@@ -418,9 +418,10 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         self.y = y_u8.reshape(-1)
         self.n_batches = self.x.shape[0] // self.batch
 
-    def _micro(self) -> tuple:
+    def _micro(self, perturbed: bool = False) -> tuple:
         """(loss_sum, correct_sum, g) of the micro-batch at the cursor (BatchNorm: its own batch
-        statistics, and one update of the running statistics)."""
+        statistics, and one update of the running statistics).  ``perturbed``: a sharpness-aware
+        step's second pass over the same batch, which leaves the running statistics alone."""
         from ..data import augment as A
 
         mixes = self.mixup_alpha > 0 or self.cutmix_alpha > 0
@@ -454,7 +455,8 @@ class CPUResNetTrainer(ResNetModel, CPUTrainerBase):
         if mixes or self.label_smoothing > 0:
             targets = torch.from_numpy(A.soft_targets(ys.cpu().numpy(), self.last_mix, self.label_smoothing,
                                                       self.spec.classes))
-        return ref_grads(self.spec, self.params, xs, ys, self.grad_scale, self.running, targets, **self._norm_kw)
+        return ref_grads(self.spec, self.params, xs, ys, self.grad_scale, None if perturbed else self.running, targets,
+                         **self._norm_kw)
 
     def evaluate(self, x_u8: torch.Tensor, y_u8: torch.Tensor, ema: bool = False):
         """Inference with the BatchNorm running statistics (eval mode); ``ema=True``: of the averaged

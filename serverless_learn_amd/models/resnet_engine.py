@@ -46,6 +46,12 @@ With ``weight_std=True`` the conv slices of the bf16 shadow hold the standardize
 from the parameters, and one ``wstd_bwd`` launch per step that takes the aggregated gradient from
 dL/dwhat back to dL/dw, ahead of the clip and the update.  The flat vector, the optimizer, the EMA
 and every exchange see the raw weights and their true gradient.
+
+With ``sam_rho > 0`` (sharpness-aware minimization, csrc/kernels/sam.hip) a step runs two forward /
+backward passes over one batch: the first, un-reduced, gives the local gradient along which three
+launches move the parameters and the shadow to w'; the second, at w' with BatchNorm momentum 0 and
+the usual bucket hooks, gives the gradient that is exchanged; one copy launch puts the saved weights
+back, and the tail above updates them.  All of it is inside the captured step.
 """
 from __future__ import annotations
 
@@ -281,6 +287,11 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             self._ce_kw = dict(ws=self.ce_ws)
         self.loss = torch.zeros(B, device=dev)
         self.correct = torch.zeros(B, device=dev)
+        # sam_rho > 0: the second pass's per-sample loss / correct, at the perturbed weights (sam_stats());
+        # loss / correct stay the first pass's, at the real ones.  Off: neither exists
+        self.sam_loss = self.sam_correct = None
+        if self.opt.sams:
+            self.sam_loss, self.sam_correct = torch.zeros_like(self.loss), torch.zeros_like(self.correct)
         self._alloc_accum()
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.x = self.y = None
@@ -399,17 +410,23 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         else:
             K.input_norm(xs, ys, self.cursor, B, self.x0, self.labels, CIFAR_MEAN, CIFAR_STD)
 
-    def forward(self, train: bool = True):
+    def forward(self, train: bool = True, perturbed: bool = False):
+        """``perturbed``: a sharpness-aware step's second pass.  x0, the labels and the mix rows are
+        still this cursor's, so no input launch runs; every launch that takes the BatchNorm momentum
+        gets 0, which leaves the running statistics the first pass's bit for bit; and the loss launch
+        writes sam_loss / sam_correct."""
         if self.norm == "group":
-            return self._forward_gn(train)
+            return self._forward_gn(train, perturbed)
         K, spec = self.K, self.spec
+        mom = 0.0 if perturbed else self.bn_momentum
         self.arena.zero_()
-        self._forward_input(train)
+        if not perturbed:
+            self._forward_input(train)
         sbn = self.bn[spec.stem_bn.name]
         self._conv_bn(self.x0, self.conv["stem"], sbn, self.c0)
         cnt0 = self.c0.numel() // 64
         if not self.stem_onload:
-            K.bn_apply_stats(self.c0, sbn, self.a0, cnt0, momentum=self.bn_momentum)
+            K.bn_apply_stats(self.c0, sbn, self.a0, cnt0, momentum=mom)
         if spec.stem == "imagenet":
             K.maxpool_fwd(self.a0, self.p0, self.p0_arg)
         for i, st in enumerate(self.blocks):
@@ -418,42 +435,44 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             stem_in = i == 0 and self.stem_onload
             if stem_in:
                 K.conv3x3_bnin_fwd(self.c0, self.conv[blk.conv1.name].w, sbn, cnt0, st["c1"], stats=b1.stats_buf,
-                                   momentum=self.bn_momentum)
+                                   momentum=mom)
             else:
                 self._conv_bn(st["x"], self.conv[blk.conv1.name], b1, st["c1"])
             cnt = st["c1"].numel() // blk.conv1.cout
             if st["bnin"]:
                 K.conv3x3_bnin_fwd(st["c1"], self.conv[blk.conv2.name].w, b1, cnt, st["c2"], stats=b2.stats_buf,
-                                   momentum=self.bn_momentum)
+                                   momentum=mom)
             else:
-                K.bn_apply_stats(st["c1"], b1, st["a1"], cnt, momentum=self.bn_momentum)
+                K.bn_apply_stats(st["c1"], b1, st["a1"], cnt, momentum=mom)
                 self._conv_bn(st["a1"], self.conv[blk.conv2.name], b2, st["c2"])
             if blk.down is not None:
                 bd = self.bn[blk.dbn.name]
                 self._conv_bn(st["x"], self.conv[blk.down.name], bd, st["cs"])
-                K.bn_apply_stats(st["c2"], b2, st["y"], cnt, res=st["cs"], rbn=bd, momentum=self.bn_momentum,
+                K.bn_apply_stats(st["c2"], b2, st["y"], cnt, res=st["cs"], rbn=bd, momentum=mom,
                                  mask_out=st["ym"])
             elif stem_in:
                 K.bn_apply_stats(st["c2"], b2, st["y"], cnt, res=self.c0, rbn=sbn, res_relu=True,
-                                 momentum=self.bn_momentum, mask_out=st["ym"])
+                                 momentum=mom, mask_out=st["ym"])
             else:
-                K.bn_apply_stats(st["c2"], b2, st["y"], cnt, res=st["x"], momentum=self.bn_momentum,
+                K.bn_apply_stats(st["c2"], b2, st["y"], cnt, res=st["x"], momentum=mom,
                                  mask_out=st["ym"])
-        self._forward_head(train)
+        self._forward_head(train, perturbed)
 
-    def _forward_head(self, train: bool) -> None:
-        """Average pool, classifier and loss (``train``: with the bias gradient and soft targets)."""
+    def _forward_head(self, train: bool, perturbed: bool = False) -> None:
+        """Average pool, classifier and loss (``train``: with the bias gradient and soft targets;
+        ``perturbed``: loss and correct go to a sharpness-aware step's scratch rows)."""
         K, spec = self.K, self.spec
+        loss, correct = (self.sam_loss, self.sam_correct) if perturbed else (self.loss, self.correct)
         K.avgpool_fwd(self.feat_in, self.feat)
         K.conv_fwd(self.feat, self.fc_w, spec.classes, 1, 1, 0, yf=self.logits, bias=self.fc_b)
         if train and (self.mixes or self.label_smoothing > 0):
             # soft targets; `correct` stays the argmax against the sample's own label (a diagnostic
             # under mixing)
-            K.softmax_ce_soft(self.logits, self.labels, self.loss, self.correct,
+            K.softmax_ce_soft(self.logits, self.labels, loss, correct,
                               self.dlogits.view(self.batch, self.logit_ld), self.fc_gb, self.grad_scale,
                               mix=self.mix_out, eps=self.label_smoothing, **self._ce_kw)
         else:
-            K.softmax_ce(self.logits, self.labels, self.loss, self.correct,
+            K.softmax_ce(self.logits, self.labels, loss, correct,
                          self.dlogits.view(self.batch, self.logit_ld), self.fc_gb if train else None,
                          self.grad_scale, **self._ce_kw)
 
@@ -589,12 +608,13 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.K.gn_bwd(dy, x, g.gamma, g.beta, g.mean, g.rstd, dx, self.gn_ws, self.norm_groups, **mask)
         self.K.gn_param_fold(self.gn_ws, self.batch, g.ggamma, g.gbeta)
 
-    def _forward_gn(self, train: bool = True) -> None:
+    def _forward_gn(self, train: bool = True, perturbed: bool = False) -> None:
         """Per block: c1 = conv(x), a1 = relu(gn1(c1)), c2 = conv(a1), y = relu(gn2(c2) + sc) with
         sc = x or gnd(conv_down(x)) and y's 1-bit mask stored.  Plain convolutions (no statistics
         epilogue), one launch per GroupNorm; the same function in training and evaluation."""
         K, spec = self.K, self.spec
-        self._forward_input(train)
+        if not perturbed:  # (a sharpness-aware step's second pass: x0 and the labels are still this cursor's)
+            self._forward_input(train)
         sc = spec.stem_conv
         K.conv_fwd(self.x0, self.conv["stem"].w, sc.cout, sc.k, sc.stride, sc.pad, y=self.c0)
         self._gn_fwd(self.c0, spec.stem_bn.name, self.a0)
@@ -610,7 +630,7 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
                 self._gn_fwd(st["cs"], blk.dbn.name, st["sc"], relu=False)
                 res = st["sc"]
             self._gn_fwd(st["c2"], blk.bn2.name, st["y"], res=res, mask_out=st["ym"])
-        self._forward_head(train)
+        self._forward_head(train, perturbed)
 
     def _backward_gn(self, hook: bool = True, fold: bool = False):
         """The mirror of :meth:`_forward_gn`; bucket hooks fire at the offsets of :meth:`backward`."""
@@ -687,7 +707,10 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
             self._accum_sums(i)
             self.K.cursor_bump(self.cursor)
             self.grad.zero_()
-        self.forward(train=True)
+        sam = self.sam_buf is not None
+        if sam:  # the first pass and the move to w'; the pass below then runs there, on the same batch
+            self._sam_perturb()
+        self.forward(train=True, perturbed=sam)
         # grad = ((g_0 + g_1) + ...) + g_last: bucket by bucket ahead of each hook, so the bucket
         # all-reduces still overlap the rest of this backward; in one launch with no bucket hook
         handles = self.backward(fold=last > 0)
@@ -702,6 +725,8 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         if self.allreduce is not None:
             self.allreduce(self.grad)
         self.phases.mark("exchange")
+        if sam:  # back to w, bit for bit; the update launch below rewrites the shadow from it
+            self.O.sam_restore(self.params, self.sam_buf)
         self._unstandardize_grad()
         if self.agc_buf is not None:  # unit by unit on the true dL/dw, ahead of the global clip (agc.hip)
             self.O.agc_clip_flat(self.params, self.grad, self.agc_buf, self.opt.agc_clip, self.opt.agc_eps)
@@ -714,6 +739,24 @@ class FusedResNetTrainer(ResNetModel, GraphedStep, TrainerState):
         self.wt()
         self.K.cursor_bump(self.cursor)
         self.phases.mark("update")
+
+    def _sam_perturb(self) -> None:
+        """sam_rho > 0 (accum_steps is 1): the first forward / backward at the real weights, with no bucket
+        hook and no exchange -- the perturbation is each replica's own, the paper's m-sharpness -- then
+        the three launches of csrc/kernels/sam.hip on the true local dL/dw: params and shadow hold w' and
+        ``sam_buf.saved`` the way back.  What the convolutions read is rebuilt from them (the norm scales
+        and shifts and fc.bias are read from params as they are), and the gradient is cleared for the
+        second pass."""
+        O, b, s = self.O, self.sam_buf, self.opt
+        self.forward(train=True)
+        self.backward(hook=False)
+        self._unstandardize_grad()
+        O.sam_norms(self.params, self.grad, b, s.sam_adaptive, s.sam_eta)
+        O.sam_scale(b, s.sam_rho)
+        O.sam_perturb(self.params, self.grad, self.shadow, b, s.sam_adaptive, s.sam_eta)
+        self._standardize()
+        self.wt()
+        self.grad.zero_()
 
     def _update(self) -> None:
         """The optimizer launch (the step-counter rules: plus the bump of the optimizer step)."""

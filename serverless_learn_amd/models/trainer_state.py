@@ -15,10 +15,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, LARS_KERNELS, MUON_KERNELS, LarsBuffers,
-                         MuonBuffers, OptSpec, agc_clip_reference, agc_summary, check_accum_steps, clip_buffers,
-                         clip_grad_, decay_vector, ema_update_, lars_plan, muon_plan, require_kernels, sgd_update,
-                         trainer_class_map)
+from ..ops.optim import (ACCUM_KERNELS, CLIP_KERNELS, EMA_KERNELS, LARS_KERNELS, MUON_KERNELS, SAM_KERNELS,
+                         LarsBuffers, MuonBuffers, OptSpec, SamBuffers, agc_clip_reference, agc_summary,
+                         check_accum_steps, clip_buffers, clip_grad_, decay_vector, ema_update_, lars_plan, muon_plan,
+                         require_kernels, sam_perturb_reference, sgd_update, trainer_class_map)
 
 
 @dataclass
@@ -65,6 +65,13 @@ class TrainerState:
     uploaded tables with the launch's stats rows; :meth:`agc_stats` reads the last step's.  Adaptive
     clipping keeps no state at all; with it off both attributes are None.
 
+    With ``sam_rho > 0`` (ResNet trainers, under any rule, ``accum_steps`` 1 only) a step takes the
+    update's gradient at weights perturbed along the first pass's local gradient (ops/optim.py
+    sam_perturb_reference).  ``sam_cls`` is the class map the perturbation reads and on a GPU ``sam_buf``
+    holds it with the chunk sums, ``(nrm, scale)`` and the saved weights; :meth:`sam_stats` reads the last
+    step's.  The perturbation is undone before the update, so SAM keeps no state: checkpoints,
+    ``buffers()`` and ``state_extra()`` gain nothing, and with it off both attributes are None.
+
     The owner sets ``params`` (``n_params`` real entries, then any padding) before
     :meth:`_init_state`, and keeps ``cursor`` (an int, or a 1-element tensor on the device)."""
 
@@ -75,6 +82,8 @@ class TrainerState:
     lars_capable = False          # optimizer="lars": the ResNet trainers (models/resnet.py ResNetModel)
     agc_plan = agc_buf = None     # agc_clip > 0: the ResNet trainers' units (ResNetModel._init_agc)
     _agc_rows = None              # CPU: the last step's (wn, gn, s) rows
+    sam_cls = sam_buf = None      # sam_rho > 0: the class map, and on a GPU its buffers (ops/optim.py SamBuffers)
+    _sam_last = None              # CPU: the last step's (nrm, scale, perturbed loss sum, perturbed correct sum)
     accum_kernels = ACCUM_KERNELS  # ... and of its accumulated step
     graph = None                  # a captured step (GPU engines: a slot of utils/graphs.py)
     grad = None                   # the aggregated gradient of the last step, as the optimizer took it
@@ -98,6 +107,10 @@ class TrainerState:
         if spec.agcs and not self.lars_capable:
             raise ValueError("agc_clip holds every filter's gradient to its weights' norm: the mlp model's fused slab "
                              "update cannot see a norm before it moves a weight (model='resnet18')")
+        if spec.sams and not self.lars_capable:
+            raise ValueError("sam_rho needs a second forward / backward at perturbed weights inside the step: the mlp "
+                             "model's fused step has none (model='resnet18')")
+        self._check_sam_accum(self.accum_steps)
         word =lambda: torch.zeros(1, dtype=torch.int32, device=self.device)  # noqa: E731
         self.mom = torch.zeros_like(self.params) if (momentum > 0 or spec.adamw or spec.muon) else None
         # AdamW's second moment (mom is its first); the optimizer step the update reads (and the
@@ -129,7 +142,17 @@ class TrainerState:
             self.muon_plan = muon_plan(self.layout(), int(self.params.numel()), self.norm_tensors())
             self.muon_buf = MuonBuffers(self.muon_plan, self.device) if self._gpu else None
             self._muon_norms = None  # CPU: the last update's ||u||_F per tensor
+        if spec.sams:  # the class map (built here if nothing above did), on a GPU with the step's buffers
+            self.sam_cls = trainer_class_map(self)
+            if self._gpu:
+                require_kernels(spec, *SAM_KERNELS)
+                self.sam_buf = SamBuffers(self.sam_cls, int(self.params.numel()), self.device)
         self._opt_tables()
+
+    def _check_sam_accum(self, k: int) -> None:
+        if self.opt.sams and k > 1:
+            raise ValueError(f"sam_rho with accum_steps={k}: a sharpness-aware step perturbs along one batch's "
+                             "gradient and has no accumulated form (accum_steps=1)")
 
     def norm_tensors(self) -> tuple:
         """Names (as in ``layout()``) of the normalisation layers' tensors: decay class 1."""
@@ -217,6 +240,23 @@ class TrainerState:
         if self._gpu:
             return agc_summary(self.agc_plan, self.agc_buf.stats.cpu().numpy())
         return agc_summary(self.agc_plan, self._agc_rows.numpy()) if self._agc_rows is not None else {}
+
+    def sam_stats(self) -> dict:
+        """``{"norm", "scale", "loss_perturbed", "correct_perturbed"}`` of the last sharpness-aware step:
+        the (adaptive) norm of the first pass's local gradient, ``sam_rho / (norm + 1e-12)`` (0 where the
+        norm was not finite), and the second pass's mean loss and accuracy at the perturbed weights
+        (``stats()`` reports the first pass's, at the real ones).  On a GPU two reads from the device;
+        empty before the first step on the CPU."""
+        if not self.opt.sams:
+            raise ValueError("this trainer is not sharpness-aware (sam_rho=0): there are no sam statistics")
+        if self._gpu:
+            (nrm, scale), n = self.sam_buf.out.tolist(), self.batch
+            return {"norm": nrm, "scale": scale, "loss_perturbed": float(self.sam_loss.sum()) / n,
+                    "correct_perturbed": float(self.sam_correct.sum()) / n}
+        if self._sam_last is None:
+            return {}
+        nrm, scale, loss, correct = self._sam_last
+        return {"norm": nrm, "scale": scale, "loss_perturbed": loss / self.batch, "correct_perturbed": correct / self.batch}
 
     def ema_flat(self) -> torch.Tensor:
         """A copy of the averaged parameters (``ema_decay > 0``)."""
@@ -308,7 +348,8 @@ class TrainerState:
         """``k`` micro-batches per optimizer step, each on its own batch (the cursor moves after
         each): their gradients are summed in fp32 in order, and the sum takes one exchange, one clip
         and one update.  The gradient scale follows (a mean over ``k * batch * world``) and a
-        captured step is dropped."""
+        captured step is dropped.  Refused above 1 on a sharpness-aware trainer."""
+        self._check_sam_accum(check_accum_steps(k))
         self.accum_steps = check_accum_steps(k)
         self._alloc_accum()
         self.set_world(self.world_size)
@@ -345,8 +386,22 @@ class CPUTrainerBase(TrainerState):
     def refresh_shadows(self) -> None:
         pass
 
+    def _sam_second_pass(self, g: torch.Tensor) -> torch.Tensor:
+        """sam_rho > 0: the gradient of the same batch at the weights perturbed along ``g``, the first
+        pass's local gradient (ops/optim.py sam_perturb_reference); the weights are put back.  The
+        subclass's ``_micro(perturbed=True)`` leaves the running statistics as the first pass set them."""
+        s, w = self.opt, self.params.clone()
+        wp, nrm, scale = sam_perturb_reference(w, g, self.sam_cls, s.sam_rho, s.sam_adaptive, s.sam_eta)
+        self.params.copy_(wp)
+        loss, correct, g2 = self._micro(perturbed=True)
+        self.params.copy_(w)
+        self._sam_last = (nrm, scale, float(loss), float(correct))
+        return g2
+
     def step(self) -> None:
         loss, correct, g = self._accumulate(self._micro)
+        if self.opt.sams:  # (accum_steps is 1: g is this batch's local gradient, ahead of any exchange)
+            g = self._sam_second_pass(g)
         self.phases.mark("compute")
         if self.allreduce is not None:
             self.allreduce(g)

@@ -38,6 +38,11 @@ clip: :func:`agc_clip_reference` is its float64 definition, :func:`agc_plan` its
 filter row, every norm vector) and :func:`agc_clip_flat` the one grouped launch
 (csrc/kernels/agc.hip).
 
+Sharpness-aware minimization (``sam_rho``, under any rule; ResNet trainers) takes the update's gradient
+at weights perturbed along the first pass's local gradient: :func:`sam_perturb_reference` is the float64
+definition of the perturbation, and :func:`sam_norms`, :func:`sam_scale` and :func:`sam_perturb` its
+three launches (csrc/kernels/sam.hip); the way back is :func:`accum_flat` from the saved vector.
+
 A weight EMA (``ema_decay``) follows every update: :func:`ema_update_` is its reference,
 :func:`ema_table` the per-step coefficients and :func:`ema_flat` the one launch that applies them and
 advances its own device-resident counter.
@@ -522,6 +527,52 @@ def agc_summary(plan: AgcPlan, rows) -> dict:
     return out
 
 
+# ---- sharpness-aware minimization (Foret et al. 2021; ASAM: Kwon et al. 2021) ----
+SAM_CHUNK = 4096   # elements per chunk of the norms launch (csrc/kernels/sam.hip SAM_CHUNK)
+SAM_EPS = 1e-12    # added to the norm under rho
+
+
+def check_sam(rho, adaptive, eta) -> None:
+    """``sam_rho``: a finite float >= 0 (0: off); ``sam_adaptive``: a bool; ``sam_eta``: a finite
+    float > 0."""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)  # noqa: E731
+    if not num(rho) or rho < 0:
+        raise ValueError(f"sam_rho must be a finite number >= 0 (0: off), got {rho!r}")
+    if not isinstance(adaptive, (bool, np.bool_)):
+        raise ValueError(f"sam_adaptive must be a bool, got {adaptive!r}")
+    if not num(eta) or eta <= 0:
+        raise ValueError(f"sam_eta must be a finite number > 0, got {eta!r}")
+
+
+def sam_perturb_reference(w: torch.Tensor, g: torch.Tensor, cls, rho: float, adaptive: bool = False,
+                          eta: float = 0.01) -> tuple:
+    """Sharpness-aware minimization's perturbed weights, in float64: ``(w', nrm, scale)``.  ``w``:
+    the flat fp32 parameters; ``g``: the first pass's local ``dL/dw`` (0 in alignment padding); ``cls``:
+    the :func:`decay_class_map` of the vector.  ``T_i = |w_i| + eta`` for a class-0 element of an
+    ``adaptive`` step (ASAM, biases and norm parameters left non-adaptive) and 1 otherwise; ``nrm =
+    sqrt(sum_i (T_i g_i)^2)``, summed per chunk of :data:`SAM_CHUNK` elements and the chunk sums then
+    folded in chunk order; ``scale = rho / (nrm + 1e-12)``, or 0 where ``nrm`` is not finite (``w'`` is
+    then ``w``: a non-finite gradient stays the clip's business); ``w'_i = float32(w_i + scale T_i T_i
+    g_i)``, evaluated left to right and rounded once."""
+    n = int(w.numel())
+    w64, g64 = w.detach().double().reshape(-1), g.detach().double().reshape(-1)
+    T = torch.ones_like(w64)
+    if adaptive:
+        per = torch.as_tensor(np.asarray(cls)).long().repeat_interleave(DECAY_BLOCK)[:n].to(w64.device)
+        assert per.numel() == n, "the class map is shorter than the vector"
+        T = torch.where(per == CLS_WEIGHT, w64.abs() + float(eta), T)
+    t = T * g64
+    sq = torch.cat([t * t, t.new_zeros(-n % SAM_CHUNK)]).view(-1, SAM_CHUNK)
+    total = 0.0
+    for p in sq.sum(dim=1).tolist():
+        total += p
+    nrm = math.sqrt(total)
+    scale = float(rho) / (nrm + SAM_EPS) if math.isfinite(nrm) else 0.0
+    if scale == 0.0:
+        return w.detach().clone().reshape(-1), nrm, scale
+    return (w64 + scale * T * T * g64).to(w.dtype), nrm, scale
+
+
 EMA_WARMUP_OFFSET = 10   # warm-up: decay_t = min(decay, (1 + t) / (10 + t))
 EMA_TABLE_MAX = 1 << 20  # entries of the warm-up table
 
@@ -612,6 +663,12 @@ class OptSpec:
     # conv filter and norm vector of the gradient is held to agc_clip * max(its weights' norm, agc_eps) (0: off)
     agc_clip: float = 0.0
     agc_eps: float = 1e-3
+    # sharpness-aware minimization, under any rule (ResNet trainers): the update's gradient is taken at weights moved
+    # sam_rho along the first pass's local gradient (0: off); sam_adaptive: ASAM, the conv / linear weights' move
+    # scaled element-wise by |w| + sam_eta.  No rule or kernel choice depends on these
+    sam_rho: float = 0.0
+    sam_adaptive: bool = False
+    sam_eta: float = 0.01
 
     def __post_init__(self):
         check_group_decay("norm_weight_decay", self.norm_weight_decay)
@@ -621,6 +678,7 @@ class OptSpec:
         check_lars(self.lars_eta, self.lars_eps)
         check_muon(self.muon_lr_ratio, self.muon_nesterov, self.muon_ns_steps)
         check_agc(self.agc_clip, self.agc_eps)
+        check_sam(self.sam_rho, self.sam_adaptive, self.sam_eta)
         if self.lr_schedule not in SCHEDULES:
             raise ValueError(f"unknown lr_schedule {self.lr_schedule!r} (choose from {SCHEDULES})")
         if self.lr_warmup_steps < 0 or self.lr_decay_steps < 0:
@@ -641,6 +699,10 @@ class OptSpec:
     @property
     def agcs(self) -> bool:
         return self.agc_clip > 0.0
+
+    @property
+    def sams(self) -> bool:
+        return self.sam_rho > 0.0
 
     @property
     def emas(self) -> bool:
@@ -761,6 +823,8 @@ class OptSpec:
                      muon_ns_steps=int(self.muon_ns_steps))
         if self.agcs:
             d.update(agc_clip=self.agc_clip, agc_eps=self.agc_eps)
+        if self.sams:
+            d.update(sam_rho=self.sam_rho, sam_adaptive=bool(self.sam_adaptive), sam_eta=self.sam_eta)
         return d
 
 
@@ -1034,6 +1098,58 @@ def agc_clip_flat(w: torch.Tensor, g: torch.Tensor, b: AgcBuffers, clip: float, 
     N.call("sl_agc_clip", N.ptr(w), N.ptr(g), w.numel(), b.units_h.ctypes.data, N.ptr(b.units), len(b.units_h),
            b.work_h.ctypes.data, N.ptr(b.work), len(b.work_h), float(clip), float(eps), N.ptr(b.stats),
            N.stream_ptr())
+
+
+SAM_KERNELS = ("sl_sam_chunk", "sl_sam_norms", "sl_sam_scale", "sl_sam_perturb", "sl_accum_flat")
+
+
+class SamBuffers:
+    """What a SAM step keeps on a device for a vector of ``n`` elements (a multiple of 64) with the class
+    map ``cls``: the map, ``partials`` (one fp64 sum per :data:`SAM_CHUNK` elements), ``out`` (fp64 ``(nrm,
+    scale)`` of the last perturbation) and ``saved`` (the unperturbed weights, the way back)."""
+
+    def __init__(self, cls: np.ndarray, n: int, device):
+        assert int(N.lib().sl_sam_chunk()) == SAM_CHUNK, "the kernel library was built with another SAM_CHUNK"
+        assert n > 0 and n % DECAY_BLOCK == 0 and len(cls) * DECAY_BLOCK == n, "whole class blocks"
+        self.n = int(n)
+        self.cls = torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)).to(device)
+        self.partials = torch.zeros((self.n + SAM_CHUNK - 1) // SAM_CHUNK, dtype=torch.float64, device=device)
+        self.out = torch.zeros(2, dtype=torch.float64, device=device)
+        self.saved = torch.zeros(self.n, dtype=torch.float32, device=device)
+
+
+def _check_sam(w: torch.Tensor, g: torch.Tensor, b: SamBuffers) -> None:
+    assert w.is_cuda and w.dtype == torch.float32 and g.dtype == torch.float32
+    assert w.is_contiguous() and g.is_contiguous() and g.numel() == w.numel()
+    assert w.numel() == b.n and b.cls.device == w.device, "the buffers were made for another vector"
+
+
+def sam_norms(w: torch.Tensor, g: torch.Tensor, b: SamBuffers, adaptive: bool = False, eta: float = 0.01) -> None:
+    """``b.partials[c]`` = the sum of ``(T_i g_i)^2`` over chunk ``c``: one launch, one workgroup per chunk,
+    fp64 products and sums in a fixed order (csrc/kernels/sam.hip sam_norms_kernel)."""
+    _check_sam(w, g, b)
+    N.call("sl_sam_norms", N.ptr(w), N.ptr(g), N.ptr(b.cls), b.n, int(bool(adaptive)), float(eta), N.ptr(b.partials),
+           b.partials.numel(), N.stream_ptr())
+
+
+def sam_scale(b: SamBuffers, rho: float) -> None:
+    """``b.out = (nrm, scale)`` from ``b.partials``, folded in chunk order by one wave (sam_scale_kernel)."""
+    N.call("sl_sam_scale", N.ptr(b.partials), b.partials.numel(), float(rho), N.ptr(b.out), N.stream_ptr())
+
+
+def sam_perturb(w: torch.Tensor, g: torch.Tensor, shadow: torch.Tensor, b: SamBuffers, adaptive: bool = False,
+                eta: float = 0.01) -> None:
+    """``b.saved = w``, ``w = w'`` and ``shadow = bf16(w')`` with ``b.out``'s scale, in one launch
+    (sam_perturb_kernel); :func:`sam_restore` undoes it."""
+    _check_sam(w, g, b)
+    assert shadow.dtype == torch.bfloat16 and shadow.numel() == w.numel() and shadow.is_contiguous()
+    N.call("sl_sam_perturb", N.ptr(w), N.ptr(g), N.ptr(b.saved), N.ptr(shadow), b.n, N.ptr(b.cls), int(bool(adaptive)),
+           float(eta), N.ptr(b.out), N.stream_ptr())
+
+
+def sam_restore(w: torch.Tensor, b: SamBuffers) -> None:
+    """``w = b.saved``: a copy (:func:`accum_flat`, ``add`` off), so the weights return bit for bit."""
+    accum_flat(w, b.saved, False)
 
 
 def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:

@@ -162,6 +162,8 @@ class Worker:
             kw.update(clip_grad_norm=c.clip_grad_norm)
         if c.agc_clip > 0:  # (Config refuses it for the MLP; a bad value is refused by Config and by OptSpec)
             kw.update(agc_clip=c.agc_clip, agc_eps=c.agc_eps)
+        if c.sam_rho > 0:  # (Config refuses it for the MLP and with accumulation)
+            kw.update(sam_rho=c.sam_rho, sam_adaptive=c.sam_adaptive, sam_eta=c.sam_eta)
         if (c.augment, c.augment_pad, c.shuffle) != ("none", 4, False):
             # (an unknown name or a bad pad is refused by the trainer, data/augment.py check)
             kw.update(augment=c.augment, augment_pad=c.augment_pad, shuffle=c.shuffle)
@@ -218,6 +220,8 @@ class Worker:
                           tensors=len(self.trainer.muon_plan.names))
         if c.agc_clip > 0:
             self.log.info("agc", clip=c.agc_clip, eps=c.agc_eps, units=len(self.trainer.agc_plan.units))
+        if c.sam_rho > 0:
+            self.log.info("sam", rho=c.sam_rho, adaptive=bool(c.sam_adaptive), eta=c.sam_eta)
         if c.ema_decay != 0:
             self.log.info("ema",decay=c.ema_decay, warmup=bool(c.ema_warmup), table=int(self.trainer.ema_tab.numel()))
         if self.cfg.sync in ("gossip", "ps"):
